@@ -13,13 +13,28 @@ cost against a 10-primitive scene, 1024 problems per GPU.  `value` is SQP
     python bench.py --config HB --batch 256     (host-loop workload, see main_hostloop)
     python bench.py --config HA                 (config B + JointAcc cost: the fused kernel's
                                                  waypoint-pair solve)
+    python bench.py --full                      (adds the lone-batch latency, the repeat checks
+                                                 and cpu_baseline, see below)
+    python bench.py --dump-outputs DIR          (the last timed step's outputs as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line: the
+headline `value`, `ms_per_step` and the roofline figures that the timed
+launches themselves yield.  Everything that takes a run of its own is behind
+`--full`: the lone-batch latency (`config.batch_latency_ms`), the checks that
+the SQP counters repeat between steps and between batch contexts, and
+`cpu_baseline`.  Without it those fields are null.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller
+(solver.download(): the trajectories `x` and one array per Result field,
+`res_<field>`) as float64 .npy files, after the timed region.  The inputs are
+seeded, so two builds run with the same arguments can be compared file by file.
 
 Batches in flight: the runtime keeps `--inflight` (default 3) batch contexts,
 each with its own HIP stream, and submits step k to context k mod inflight,
 so the next batch's problems fill the CUs that the current batch's last
 (longest) problems leave idle.  Every step still solves a full batch of
 `--batch` problems from its own HBM-resident inputs; `batch_latency_ms` is one
-batch alone (no overlap), measured before the timed region.
+batch alone (no overlap), measured before the timed region (--full).
 
 Multi-GPU: one process per GPU (torchrun); every rank solves its own
 contiguous shard of problem seeds (weak scaling, no data-path collective); a
@@ -33,8 +48,8 @@ Extra JSON objects:
                 bytes over the timed region (achieved_per_step_gbs), the
                 PMC-measured traffic rate (measured_gbs) and what actually
                 limits the kernel (limiter).
-  cpu_baseline  the oracle's CPU restatement (oracle/, "port") on a bounded
-                sample of the same problems, rank 0 at N=1 only.
+  cpu_baseline  (--full) the oracle's CPU restatement (oracle/, "port") on a
+                bounded sample of the same problems, rank 0 at N=1 only.
 """
 from __future__ import annotations
 
@@ -145,6 +160,34 @@ def host_cpus():
     return usable, nproc, model, quota
 
 
+def _workload_chunk(job):
+    config, n, first = job
+    wl = problems.make_workload(config, n, first_problem=first)
+    return wl.init, wl.targets, wl.scene, wl.q_ref, wl.jpos_targets
+
+
+def rank_workload(config, batch, rank, world):
+    """sharding.rank_workload(config, batch, rank) with its problems generated by
+    worker processes.  The generator is pure Python (config C places every
+    scene primitive by rejection sampling: half a minute for 1024 problems on
+    one core) and seeds every problem by its own index, so contiguous chunks
+    concatenate to exactly the arrays of one call.  Forks, so it is called
+    before torch is imported and the GPU is opened."""
+    jobs = max(1, min(16, host_cpus()[0] // max(1, world), batch // 16))
+    if jobs == 1:
+        return sharding.rank_workload(config, batch, rank)
+    import multiprocessing as mp
+
+    first = sharding.shard_first(rank, batch)
+    cuts = [batch * j // jobs for j in range(jobs + 1)]
+    with mp.get_context("fork").Pool(jobs) as pool:
+        parts = pool.map(_workload_chunk, [(config, hi - lo, first + lo) for lo, hi in zip(cuts[:-1], cuts[1:])])
+    one = problems.make_workload(config, 1, first_problem=first)  # the description every problem shares
+    init, targets, scene, q_ref = (np.concatenate([p[i] for p in parts]) for i in range(4))
+    jpos = None if one.jpos_targets is None else np.concatenate([p[4] for p in parts])
+    return problems.Workload(one.name, one.desc, init, targets, scene, q_ref, jpos)
+
+
 def cpu_baseline(config, n_problems, threads):
     """The oracle (CPU restatement of the reference path) timed on a bounded
     sample of the same problems: its -O3 FMA build for the host's ISA level
@@ -210,6 +253,32 @@ def pmc_evidence(config):
     return best
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, x, results, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step, (x [B, N, D], results [B]), as float64 arrays <name>.npy (with a
+    _rank<r> suffix at N > 1).  A batch whose arrays exceed DUMP_MAX_BYTES is
+    cut to a fixed seeded sample of its problems, named in problem_index."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    B = x.shape[0]
+    fields = [f[0] for f in abi.Result._fields_]
+    per_problem = 8 * (int(np.prod(x.shape[1:])) + len(fields) + 1)
+    keep = np.arange(B)
+    if B * per_problem > DUMP_MAX_BYTES:
+        n = max(1, DUMP_MAX_BYTES // per_problem)
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+    arrays = {"x": np.asarray(x, dtype=np.float64)[keep], "problem_index": keep.astype(np.float64)}
+    for f in fields:
+        arrays[f"res_{f}"] = np.array([getattr(results[b], f) for b in keep], dtype=np.float64)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}{suffix}.npy", a)
+
+
 HOSTLOOP_BASE = "B"  # bench --config HB: config B's problems + JointAcc and JointJerk costs
 
 
@@ -266,10 +335,13 @@ def main_hostloop(args, world, rank, local_rank, json_out):
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    res_last = outs[-1][1]
-    for _, r in outs[:-1] + ([(None, res0)] if res0 is not None else []):
-        if any(a.n_sqp_iters != b.n_sqp_iters or a.n_admm_iters != b.n_admm_iters for a, b in zip(r, res_last)):
-            raise SystemExit("non-deterministic SQP counters between steps")
+    x_last, res_last = outs[-1]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x_last, res_last, rank, world)
+    if args.full:  # every step solves copies of the same problems: the counters must repeat exactly
+        for _, r in outs[:-1] + ([(None, res0)] if res0 is not None else []):
+            if any(a.n_sqp_iters != b.n_sqp_iters or a.n_admm_iters != b.n_admm_iters for a, b in zip(r, res_last)):
+                raise SystemExit("non-deterministic SQP counters between steps")
     st = [batches[args.warmup + k].stats() for k in range(args.steps)]
     iters_local = sum(r.n_sqp_iters for r in res_last)
     elapsed, iters_total = sharding.reduce_step_stats(elapsed, iters_local, world)
@@ -323,7 +395,7 @@ def main_hostloop(args, world, rank, local_rank, json_out):
             },
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             sys.path.insert(0, str(ROOT))
             from oracle import oracle  # checker / baseline only
 
@@ -358,7 +430,13 @@ def main():
     ap.add_argument("--inflight", type=int, default=3, help="batch contexts (streams) in flight")
     ap.add_argument("--cpu-problems", type=int, default=0, help="0: max(128, 2 x threads), at most 1024")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every CPU this process may use")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure one batch alone (config.batch_latency_ms), check that the SQP counters repeat "
+                         "between steps and batch contexts, and time the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (x and every Result field) as "
+                         "DIR/<name>.npy, float64")
     ap.add_argument("--diag-util", action="store_true",
                     help="diagnostic: per-problem cycle/wall counters over the timed steps (phase timers on; "
                          "~1 %% slower) -> CU utilisation and shader clock on stderr")
@@ -381,6 +459,8 @@ def main():
     if args.config == "HB":
         return main_hostloop(args, world, rank, local_rank, json_out)
 
+    wl = rank_workload(args.config, args.batch, rank, world)  # (worker processes: before torch and HIP are loaded)
+
     import torch
     import torch.distributed as dist
 
@@ -391,7 +471,6 @@ def main():
 
     from trajopt_amd.runtime import BatchTrustRegionSQP
 
-    wl = sharding.rank_workload(args.config, args.batch, rank)
     # one GPU per rank; ranks beyond the visible GPUs share them (a rehearsal of the N > 1
     # path on a smaller box -- the weak-scaling numbers are only meaningful with one GPU each)
     device = local_rank % max(1, torch.cuda.device_count())
@@ -409,16 +488,18 @@ def main():
     for _ in range(args.warmup):
         for s in solvers:
             s.run()
-    res = solver.download()[1] if args.warmup > 0 else None
+    res = solver.download()[1] if args.full and args.warmup > 0 else None
     # one batch alone (no other batch in flight): the per-batch latency.  Every
     # context's warmup launches must have drained first, else this launch shares
     # the CUs with their tails
     for s in solvers:
         s.sync()
     torch.cuda.synchronize()
-    solver.run()
-    solver.sync()
-    batch_latency_ms = solver.kernel_ms()
+    batch_latency_ms = None
+    if args.full:
+        solver.run()
+        solver.sync()
+        batch_latency_ms = solver.kernel_ms()
 
     def barrier():
         if world > 1:
@@ -453,13 +534,19 @@ def main():
         print(f"diag-util: {n_cu} CUs busy {100 * busy / (n_cu * elapsed):.1f} % of {elapsed:.2f} s; "
               f"shader clock {pf[:, 13].sum() / pf[:, 14].sum() * 100:.0f} MHz; mean problem "
               f"{busy / (len(solvers) and args.steps * wl.batch) * 1e3:.1f} ms", file=sys.stderr)
-    x_last, res_last = solver.download()
-    for s in solvers[1:min(len(solvers), args.steps)]:  # the contexts that ran a timed step
-        _, r2 = s.download()
-        if any(a.n_sqp_iters != b.n_sqp_iters or a.n_admm_iters != b.n_admm_iters for a, b in zip(r2, res_last)):
-            raise SystemExit("batch contexts disagree on the same problems")
+    last = solvers[(args.steps - 1) % len(solvers)]  # the context that ran the last timed step
+    x_last, res_last = last.download()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x_last, res_last, rank, world)
+    if args.full:
+        for s in solvers[:min(len(solvers), args.steps)]:  # the contexts that ran a timed step
+            if s is last:
+                continue
+            _, r2 = s.download()
+            if any(a.n_sqp_iters != b.n_sqp_iters or a.n_admm_iters != b.n_admm_iters for a, b in zip(r2, res_last)):
+                raise SystemExit("batch contexts disagree on the same problems")
 
-    # every step solves the same problems: the counters must repeat exactly
+    # every step solves the same problems: the counters must repeat exactly (--full)
     same = res is None or all(a.n_sqp_iters == b.n_sqp_iters and a.n_admm_iters == b.n_admm_iters
                               for a, b in zip(res, res_last))
     if not same:
@@ -529,7 +616,7 @@ def main():
             },
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_problems, args.cpu_threads)
         print(json.dumps(out), file=json_out, flush=True)
 

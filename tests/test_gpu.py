@@ -943,7 +943,7 @@ def test_smoke_entry():
 def test_bench_json_line():
     repo = abi.PKG_DIR.parent
     p = subprocess.run([sys.executable, str(repo / "bench.py"), "--batch", "64", "--steps", "3", "--warmup", "0",
-                        "--cpu-problems", "8"], capture_output=True, text=True, timeout=600, cwd=repo)
+                        "--full", "--cpu-problems", "8"], capture_output=True, text=True, timeout=600, cwd=repo)
     assert p.returncode == 0, p.stderr
     line = json.loads(p.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -956,6 +956,36 @@ def test_bench_json_line():
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0
     assert cb["host_nproc"] >= 1 and cb["single_problem_latency_s"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run measures the headline only (the --full fields are null) and
+    --dump-outputs writes the last timed step's (x, results) as float64 arrays.
+    The inputs are seeded and every problem is solved by one workgroup in a
+    fixed order, so the dump equals an in-process solve of the same batch bit
+    for bit."""
+    repo = abi.PKG_DIR.parent
+    p = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--batch", "64", "--steps", "2",
+                        "--warmup", "0", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, cwd=repo)
+    assert p.returncode == 0, p.stderr
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "SQP iters/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["cpu_baseline"] is None and line["config"]["batch_latency_ms"] is None
+    assert line["roofline"]["frac"] > 0
+    wl = sharding.rank_workload("C", 64, 0)
+    x, res, _ = solve_gpu(wl)
+    files = {f.stem: np.load(f) for f in (tmp_path / "out").glob("*.npy")}
+    assert set(files) == {"x", "problem_index"} | {f"res_{f[0]}" for f in abi.Result._fields_}
+    assert all(a.dtype == np.float64 and a.shape[0] == 64 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert np.array_equal(files["problem_index"], np.arange(64))
+    print("max |x_dump - x|", np.abs(files["x"] - x).max())
+    assert np.array_equal(files["x"], x)
+    for f in ("status", "n_sqp_iters", "n_admm_iters", "total_cost"):
+        assert np.array_equal(files[f"res_{f}"], np.array([getattr(r, f) for r in res], dtype=np.float64)), f
+    assert line["config"]["sqp_iters_per_step"] == int(files["res_n_sqp_iters"].sum())
 
 
 def test_joint_pos_reference_unit(oracle_mod):

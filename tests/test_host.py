@@ -53,6 +53,64 @@ def test_shard_ranges_partition_the_seed_space():
         sharding.shard_first(-1, 4)
 
 
+def test_bench_parallel_workload_equals_serial():
+    """bench.py generates its workload in worker processes: chunk by chunk it is
+    the workload of one sharding.rank_workload call, description included.
+    (A fresh process, as bench.py is: the workers are forked.)"""
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    code = """if True:
+        import numpy as np
+        import bench
+        from trajopt_amd import sharding
+        a = bench.rank_workload("C", 32, 1, 1)
+        b = sharding.rank_workload("C", 32, 1)
+        for f in ("init", "targets", "scene", "q_ref"):
+            np.testing.assert_array_equal(getattr(a, f), getattr(b, f))
+        assert a.jpos_targets is None and b.jpos_targets is None
+        assert a.name == b.name and bytes(a.desc) == bytes(b.desc)
+        print("identical", len(a.init))
+    """
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120,
+                       cwd=Path(__file__).resolve().parent.parent)
+    assert p.returncode == 0 and p.stdout.split() == ["identical", "32"], p.stdout + p.stderr
+
+
+def test_bench_dump_outputs_writes_float64_and_caps_size(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: x and every Result field as float64; a batch
+    over the size limit is cut to the same seeded sample of problems each time."""
+    import bench
+    from trajopt_amd import abi
+
+    B = 40
+    x = np.arange(B * 5 * 3, dtype=np.float64).reshape(B, 5, 3)
+    res = [abi.Result(status=b % 3, n_sqp_iters=b, n_admm_iters=10 * b, total_cost=0.5 * b) for b in range(B)]
+    names = {"x", "problem_index"} | {f"res_{f[0]}" for f in abi.Result._fields_}
+
+    bench.dump_outputs(tmp_path / "all", x, res, 0, 1)
+    got = {f.stem: np.load(f) for f in (tmp_path / "all").glob("*.npy")}
+    assert set(got) == names and all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got["x"], x)
+    np.testing.assert_array_equal(got["problem_index"], np.arange(B))
+    np.testing.assert_array_equal(got["res_n_admm_iters"], 10.0 * np.arange(B))
+    np.testing.assert_array_equal(got["res_total_cost"], 0.5 * np.arange(B))
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2048)
+    for d in ("cut1", "cut2"):
+        bench.dump_outputs(tmp_path / d, x, res, 1, 2)
+    a, b = ({f.stem: np.load(f) for f in (tmp_path / d).glob("*.npy")} for d in ("cut1", "cut2"))
+    assert set(a) == {n + "_rank1" for n in names}
+    assert sum(v.nbytes for v in a.values()) <= 2048
+    keep = a["problem_index_rank1"].astype(int)
+    assert 0 < len(keep) < B and np.all(np.diff(keep) > 0)
+    np.testing.assert_array_equal(a["x_rank1"], x[keep])
+    np.testing.assert_array_equal(a["res_n_sqp_iters_rank1"], keep.astype(np.float64))
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

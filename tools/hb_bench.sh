@@ -8,7 +8,7 @@ mkdir -p $O
 (while sleep 50; do date >> gpurun_out/tick.log; done) &
 TICK=$!
 trap 'kill $TICK' EXIT
-timeout -k 10 400 python3 -u bench.py --config HB --batch 256 --steps 1 --warmup 0 > $O/${ROUND}_bench_HB.json 2> gpurun_out/bench_HB.err
+timeout -k 10 400 python3 -u bench.py --full --config HB --batch 256 --steps 1 --warmup 0 > $O/${ROUND}_bench_HB.json 2> $O/bench_HB.err
 rm -rf gpurun_out/prof_hb
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_hb -o hb -- \
   python3 bench.py --config HB --batch 64 --steps 1 --warmup 0 --no-cpu > gpurun_out/prof_hb.log 2>&1

@@ -22,7 +22,7 @@ timeout -k 10 300 python3 -u tools/latency_model.py "$ROUND" C 1024 > gpurun_out
 bash tools/pmc_latency.sh "$ROUND" C 1024 > gpurun_out/pmc_C.log 2>&1
 bash tools/collect_profiles.sh "$ROUND"
 timeout -k 10 300 python3 -u tools/phase_profile.py C 1024 > "profiles/${ROUND}_phase_profile_C.txt" 2>&1
-timeout -k 10 400 python3 -u bench.py --config HA --batch 1024 --steps 6 --warmup 1 \
+timeout -k 10 400 python3 -u bench.py --full --config HA --batch 1024 --steps 6 --warmup 1 \
   > "profiles/${ROUND}_bench_HA.json" 2> gpurun_out/bench_HA.err
 rm -rf gpurun_out/prof_ha
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_ha -o ha -- \
