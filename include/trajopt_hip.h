@@ -586,6 +586,9 @@ int thip_debug_layout(thip_ctx* ctx, long long* doff, long long* ioff, long long
                                          (its own compilation, no segment code) */
 #define THIP_DEBUG_MAIN_BUILD 32      /* QPs outside the segment's domain run the main build's generic step
                                          instead of the generic-step build (the default since round 6) */
+#define THIP_DEBUG_SEG_REBUILD 64     /* the ADMM segment rebuilds its chain pack and hinge-row set-up at every
+                                         call instead of once per factorisation / per QP (bitwise the same
+                                         results) */
 int thip_debug_set_path(int flags);
 int thip_debug_workspace(thip_ctx* ctx, double* dws, int* iws);
 /* The solve layout a context chose (diagnostic): out[0] block-solve branches

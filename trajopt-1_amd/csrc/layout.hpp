@@ -227,6 +227,9 @@ struct Layout
   // resident; seg_slots = column/row slots per thread (1 or 2)
   int seg_ok;
   int seg_slots;
+  // diagnostic (THIP_DEBUG_SEG_REBUILD): the segment and factor() rebuild their
+  // per-QP / per-factorisation packs at every call (Ctl's stamps read as stale)
+  int seg_rebuild;
   // middle block of the twisted block factorisation (N / 2)
   int tw_mid;
   // Branches of the block solve.  A kinematic tree whose terms never touch two
@@ -359,7 +362,9 @@ struct KernelArgs
   int* work;
 };
 
-constexpr int kHPack = 14;  // doubles per hinge row in A_HPK
+// doubles per hinge row in A_HPK: z, z_bound, y, y_bound, x, u, DG, w, the
+// bound-row coefficient, q, the first x column, 1 / (DG + rho w^2)
+constexpr int kHPack = 12;
 constexpr int kHChunk = 8;  // hinge rows per gather chunk (rows of one step pair)
 constexpr int kProfSlots = 40;
 

@@ -143,6 +143,14 @@ struct Ctl
   int flags;          // sticky THIP_FLAG_* of the run
   long long n_contact_rows, n_hinge_admm, n_substates;
   int hcp[THIP_MAX_STEPS + 1];  // first hinge chunk of each step pair (admm_segment)
+  // Validity stamps of what the ADMM segment and factor() build once and reuse
+  // (written by thread 0, read by all threads after a later barrier).
+  // qp_stamp, cleared at qp_solve() entry: bit 0 the hinge chunk table, hcp and
+  // A_HCT (factor()), bit 1 the hinge pack A_HPK's constants and state
+  // (admm_segment).  fac_stamp, cleared by every factor(): the chain pack A_CPK
+  // and the pack's DG and 1 / (DG + rho w^2) fields (admm_segment).
+  // Layout::seg_rebuild reads both as always stale.
+  int qp_stamp, fac_stamp;
   int subcnt[THIP_MAX_STEPS];       // contact scan: LVS sub-states of each collision unit
   int suboff[THIP_MAX_STEPS + 1];   // and their prefix (the batched sub-state FK)
   int hboff[THIP_MAX_STEPS + 1];    // first I_HBITS word of each unit (batched scans)
@@ -225,7 +233,8 @@ __device__ __forceinline__ const gbl_f64* gbl(const double* p) { return (const g
 // 8 solve rhs + block diag (segment: phase A), 9 forward chain, 10 backward
 // chain, 11 aux back-substitution (segment: phase E), 12 qp_solve, 13 sqp
 // total, 14 sqp total (wall clock, 100 MHz ticks), 15 segment phase B
-// (rhs + Linv b), 16 segment phase C2 (Linv^T y + middle block).
+// (rhs + Linv b), 16 segment phase C2 (Linv^T y + middle block), 37 segment
+// set-up (entry to the first iteration), 38 segment write-back.
 struct ProfScope
 {
   long long* p;
@@ -2431,7 +2440,7 @@ __device__ __noinline__ void twisted_factor_half(Ctx& c, Solver& sv, const doubl
   }
 }
 
-__device__ int build_hinge_chunks(Ctx& c);
+__device__ int build_hinge_chunks(Ctx& c, bool build = false);
 __device__ __forceinline__ bool lds_resident(const Ctx& c, const double* p);
 
 // the QP's ADMM iterations run the register-resident segment (qp_solve); it
@@ -2453,6 +2462,11 @@ __device__ bool factor(Ctx& c, Solver& sv, double sigK, bool polish, double delt
   const double *PD = c.a(A_PD), *PO = c.a(A_PO), *BS = c.a(A_BS), *GS = c.a(A_GS), *WS = c.a(A_WS),
                *FS = c.a(A_FS);
   double *DG = c.a(A_DG), *RE = c.a(A_RE), *KB = c.a(A_KB), *LI = c.a(A_LINV);
+  // (read by every thread before the first barrier below; thread 0 sets bit 0
+  // after the barrier that ends the hinge set-up)
+  const bool hinge_built = (c.s->qp_stamp & 1) && !L.seg_rebuild;
+  if (c.tid == 0)
+    c.s->fac_stamp = 0;  // the segment's chain pack and DG fields are of the previous factor
   FOR(col, c.nc())
   {
     const double rb = rho_k(c, bound_row(L, col), polish, delta);
@@ -2482,11 +2496,13 @@ __device__ bool factor(Ctx& c, Solver& sv, double sigK, bool polish, double delt
   // the hinge chunk table for reduced_solve's row-parallel column sums (the
   // QP's hinge rows are fixed from here to its last solve), and the field-major
   // copy of the hinge coefficients its back-substitution reads (A_HCT, odd
-  // stride; the ADMM segment builds the same): one coalesced load per
-  // coefficient and wave instead of 2 D loads that each touch 64 cache lines
-  build_hinge_chunks(c);
-  if (nh > 0 && !seg_path(c))  // (the segment builds its own copy)
+  // stride; the ADMM segment reads the same copy): one coalesced load per
+  // coefficient and wave instead of 2 D loads that each touch 64 cache lines.
+  // Built by the QP's first factor() and kept to its last solve (qp_stamp bit
+  // 0): nothing else writes A_HCHK, hcp or A_HCT.
+  if (nh > 0 && !hinge_built)
   {
+    build_hinge_chunks(c, true);
     const int nhs = nh | 1;
     const double* HC = c.a(A_HC);
     double* HCT = c.a(A_HCT);
@@ -2496,6 +2512,8 @@ __device__ bool factor(Ctx& c, Solver& sv, double sigK, bool polish, double delt
       HCT[k * nhs + h] = HC[e];
     }
     BSYNC();
+    if (c.tid == 0)
+      c.s->qp_stamp |= 1;
   }
   // waypoint t's diagonal block entry (i, j): P, sigma + bound rows, the fixed
   // rows, its CartPose rows and the hinge rows of pairs t and t - 1 (the row
@@ -3661,14 +3679,22 @@ __device__ __forceinline__ double row_ax(const Ctx& c, int r, const double* x)
 
 // Hinge chunk table: chunks of kHChunk rows inside each step pair
 // (c.s->hcp: first chunk of each pair; A_HCHK: (first row, end row)).
-// Returns the chunk count.  Also used by the ADMM segment.
-__device__ int build_hinge_chunks(Ctx& c)
+// Returns the chunk count.  Also used by the ADMM segment.  The QP's first
+// factor() builds the table (build = true); every later caller of the QP gets
+// the kept count (Ctl::qp_stamp bit 0) behind one barrier, or rebuilds under
+// Layout::seg_rebuild.
+__device__ int build_hinge_chunks(Ctx& c, bool build)
 {
   const int N = c.L.N, nh = c.s->n_h;
   const int* HP = c.ia(I_HPTR);
   int* CHK = reinterpret_cast<int*>(c.a(A_HCHK));
   if (nh == 0)
     return 0;
+  if (!build && (c.s->qp_stamp & 1) && !c.L.seg_rebuild)
+  {
+    BSYNC();  // (the callers' stores before the table's use, as the build's barriers ordered them)
+    return c.s->hcp[N];
+  }
   if (c.tid == 0)
   {
     int acc = 0;
@@ -4313,7 +4339,12 @@ __device__ void admm_step(Ctx& c, Solver& sv, bool pre_ready)
 // updates).  The arithmetic (operation order and expression shapes) is that
 // of admm_step() + reduced_solve(), so both paths give identical iterates.
 // State is written back to A_XA0/A_Z0/A_Y/A_DX/A_DY at the end of the segment
-// for the residual / termination / rho-update / polish code.
+// for the residual / termination / rho-update / polish code.  qp_solve() calls
+// the segment once per termination-check interval; what changes only per QP
+// (the hinge rows' pack, chunk table and coefficient copy) or per
+// factorisation (the chain pack, the pack's DG fields) is built by the first
+// call that needs it and kept under Ctl::qp_stamp / fac_stamp (DESIGN.md 4,
+// round 7).
 // ---- fused twisted solve of the ADMM segment ------------------------------
 // K x = b with the twisted block factor (factor()), one pass per half on the
 // two chain waves, the factor's blocks in registers for the whole segment:
@@ -4351,15 +4382,21 @@ struct SegChain
 // ROW-output step (odd r) element (i, k); the backward block N'_t the other
 // way round.  Entries past the half's length, outside the D x D block, and the
 // right-hand-side slots are zero.  All threads; ends with a barrier.
-__device__ void seg_chain_pack(const Ctx& c, const Solver& sv, SegChain& ch)
+// fill = false: the pack is still that of the current factorisation
+// (Ctl::fac_stamp) and only the lane's SegChain is set up.  The zero regions
+// stay valid with it: phase B stores only the slots of active columns (t < N,
+// i < D: steps r < R of a half), the hand-off store of seg_chain_solve only
+// the slots k < D of the two halves, where a missing half stores the exact 0
+// its zero steps produce, and nothing else writes the pack.
+__device__ void seg_chain_pack(const Ctx& c, const Solver& sv, SegChain& ch, bool fill)
 {
   const int D = c.L.D, DD = D * D, N = c.L.N, m = c.L.tw_mid;
   lds_f64* P = lds(c.a(A_CPK));
   const lds_f64* LI = lds(c.a(A_LINV));
-  const double* M = sv.M;  // LDS or HBM (Layout::chm_hbm): generic loads, once per segment
+  const double* M = sv.M;  // LDS or HBM (Layout::chm_hbm): generic loads, once per factorisation
   const double* Nb = sv.Nb;
   const int Rh[2] = { m, N - 1 - m };
-  for (int e = c.tid; e < 2 * kCpkSteps * 64; e += kBlock)
+  for (int e = c.tid; fill && e < 2 * kCpkSteps * 64; e += kBlock)
   {
     const int h = e / (kCpkSteps * 64), r = (e / 64) % kCpkSteps, lane = e & 63;
     const int i = lane >> 3, k = lane & 7;
@@ -4376,7 +4413,7 @@ __device__ void seg_chain_pack(const Ctx& c, const Solver& sv, SegChain& ch)
     P[kCpkLM + 2 * e + 1] = mf;
     P[kCpkNB + e] = nb;
   }
-  for (int e = c.tid; e < kCpk - kCpkB; e += kBlock)
+  for (int e = c.tid; fill && e < kCpk - kCpkB; e += kBlock)
     P[kCpkB + e] = 0.0;
   {
     const int i = c.lane >> 3, k = c.lane & 7;
@@ -4561,6 +4598,7 @@ template <int CS, int AS>
 __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
 {
   PROF(0);
+  const long long t_in = (c.tid == 0 && c.s->prof) ? clock64() : 0;  // seg_setup: from here to the loop
   // the Ctx fields the iterations use, in registers: the Ctx itself lives in
   // private memory and is re-read with dependent FLAT loads after every store
   // the compiler cannot prove does not alias it
@@ -4582,39 +4620,60 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
   double* HPK = c.a(A_HPK);
 #define HP_(f) HPK[(f) * nh + h]
   // pack fields: 0 z, 1 z_bound, 2 y, 3 y_bound, 4 x (hinge variable), 5 u,
-  // 6 DG, 7 w, 8 bound-row coefficient, 9 q, 10 rn, 11 eta (A -> E scratch),
-  // 12 first x column, 13 1 / (DG + rho w^2).  Both rows of a hinge are
+  // 6 DG, 7 w, 8 bound-row coefficient, 9 q, 10 first x column,
+  // 11 1 / (DG + rho w^2).  Both rows of a hinge are
   // inequalities (u finite, l = -inf; bound row l = 0, u = +inf), so their
   // rho is the scalar rho (set_rho_vec) and only the finite bounds are kept.
   const double rho_s = c.s->rho, rho_si = 1.0 / rho_s;
-  for (int h = tid; h < nh; h += kBlock)
-  {
-    const int rh = mb + 2 * h, rb = rh + 1, col = ncb + h;
-    HP_(0) = Z[rh];
-    HP_(1) = Z[rb];
-    HP_(2) = Y[rh];
-    HP_(3) = Y[rb];
-    HP_(4) = XA[col];
-    HP_(5) = Up[rh];
-    HP_(6) = DG[col];
-    HP_(7) = HW[h];
-    HP_(8) = BS[col];
-    HP_(9) = Q[col];
-    HP_(12) = static_cast<double>(HT[h] * D);
-    HP_(13) = 1.0 / (DG[col] + rho_s * HW[h] * HW[h]);
-  }
-  // field-major copy of the hinge coefficients (odd stride)
+  // What earlier segments of this QP / this factorisation left valid (Ctl's
+  // stamps, set below after the chain pack's barrier).  Between two segments of
+  // a QP run only check_termination, the infeasibility checks, the rho update
+  // and factor(): none of them writes A_HPK, A_HCT, A_HCHK, hcp or A_CPK, the
+  // pack's state fields change in ADMM iterations only, and DG and rho in a
+  // rho update, which ends in factor().
+  const bool qp_kept = (c.s->qp_stamp & 2) && !L.seg_rebuild;
+  const bool fac_kept = qp_kept && c.s->fac_stamp && !L.seg_rebuild;
+  if (!qp_kept)
+    for (int h = tid; h < nh; h += kBlock)
+    {
+      const int rh = mb + 2 * h, rb = rh + 1, col = ncb + h;
+      HP_(0) = Z[rh];
+      HP_(1) = Z[rb];
+      HP_(2) = Y[rh];
+      HP_(3) = Y[rb];
+      HP_(4) = XA[col];
+      HP_(5) = Up[rh];
+      HP_(6) = DG[col];
+      HP_(7) = HW[h];
+      HP_(8) = BS[col];
+      HP_(9) = Q[col];
+      HP_(10) = static_cast<double>(HT[h] * D);
+      HP_(11) = 1.0 / (DG[col] + rho_s * HW[h] * HW[h]);
+    }
+  else if (!fac_kept)
+    for (int h = tid; h < nh; h += kBlock)
+    {
+      const int col = ncb + h;
+      HP_(6) = DG[col];
+      HP_(11) = 1.0 / (DG[col] + rho_s * HW[h] * HW[h]);
+    }
+  // field-major copy of the hinge coefficients (odd stride) and the hinge
+  // chunk table (chunks of kHChunk rows inside each step pair): factor() built
+  // both for this QP
   const int nhs = nh | 1;
   double* HCT = c.a(A_HCT);
-  FOR(e, nh * 2 * D)
-  {
-    const int h = e / (2 * D), k = e - h * 2 * D;
-    HCT[k * nhs + h] = HC[e];
-  }
-  // hinge chunk table: chunks of kHChunk rows inside each step pair
   int* CHK = reinterpret_cast<int*>(c.a(A_HCHK));
   double* PART = c.a(A_HPART);
-  const int nchk = build_hinge_chunks(c);
+  int nchk = (nh > 0) ? c.s->hcp[N] : 0;
+  if (L.seg_rebuild)
+  {
+    FOR(e, nh * 2 * D)
+    {
+      const int h = e / (2 * D), k = e - h * 2 * D;
+      HCT[k * nhs + h] = HC[e];
+    }
+    nchk = build_hinge_chunks(c);
+  }
   if (tid == 0)
     c.s->cur = 0;
   // MR, the chunk table and the chunk sums are LDS-resident (qp_solve checks
@@ -4628,18 +4687,18 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
   const int* const CHKc = CHK;
   const __attribute__((address_space(3))) int* const CHKl = (const __attribute__((address_space(3))) int*)CHKc;
   const bool pk_l = lds_resident(c, HPK), hct_l = lds_resident(c, HCT);
-  // phase A, hinge rows: multipliers MR_h; rn, eta kept in the pack
+  // phase A, hinge rows: multipliers MR_h.  Stand-alone for the first
+  // iteration of a segment only (rho may have changed since the last one): the
+  // later iterations' phase A is the tail of the previous phase E (hinge_e)
   auto hinge_a = [&](auto PKP) {
     for (int h = tid; h < nh; h += kBlock)
     {
       const double zh = PKP[h], zb = PKP[nh + h], yh = PKP[2 * nh + h], yb = PKP[3 * nh + h];
       const double xa = PKP[4 * nh + h], dn = PKP[6 * nh + h], w = PKP[7 * nh + h], bs = PKP[8 * nh + h];
-      const double q = PKP[9 * nh + h], deni = PKP[13 * nh + h];
+      const double q = PKP[9 * nh + h], deni = PKP[11 * nh + h];
       const double eta = rho_s * zh - yh;
       const double rn = (sig * xa - q) + bs * (rho_s * zb - yb);
       MRl[nr + h] = (eta * dn - rho_s * w * rn) * deni;
-      PKP[10 * nh + h] = rn;
-      PKP[11 * nh + h] = eta;
     }
   };
   // phase B': hinge-row share of the waypoint rhs, row-parallel: 16 lanes
@@ -4666,16 +4725,24 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
       }
   };
   // phase E, hinge rows: hinge variable, z~ = A x~, relaxed z/y/x updates
-  // (admm_row_update with the infinite bound dropped)
+  // (admm_row_update with the infinite bound dropped), then phase A of the
+  // next iteration from the updated state in registers (hinge_a's
+  // expressions): thread h owns row h in both phases, no barrier lay between
+  // them, and MR[nr + h] is read only by hinge_gather_seg behind the loop-top
+  // barrier.  This iteration's rn / eta are recomputed the same way from the
+  // state it loads.  The last iteration of a segment writes no MR (the
+  // residual epilogue puts y there).
   auto hinge_e = [&](auto PKP, auto HTP, bool last) {
     for (int h = tid; h < nh; h += kBlock)
     {
       // every pack field is read before any store (the stores could alias
       // them as far as the compiler knows)
-      const int t0 = static_cast<int>(PKP[12 * nh + h]);
+      const int t0 = static_cast<int>(PKP[10 * nh + h]);
       const double zh = PKP[h], zb = PKP[nh + h], yh = PKP[2 * nh + h], yb = PKP[3 * nh + h];
-      const double xo = PKP[4 * nh + h], uh = PKP[5 * nh + h], w = PKP[7 * nh + h], bs = PKP[8 * nh + h];
-      const double rn = PKP[10 * nh + h], eta = PKP[11 * nh + h], deni = PKP[13 * nh + h];
+      const double xo = PKP[4 * nh + h], uh = PKP[5 * nh + h], dn = PKP[6 * nh + h], w = PKP[7 * nh + h];
+      const double bs = PKP[8 * nh + h], q = PKP[9 * nh + h], deni = PKP[11 * nh + h];
+      const double eta = rho_s * zh - yh;
+      const double rn = (sig * xo - q) + bs * (rho_s * zb - yb);
       double g0 = 0, g1 = 0;
       // clamped indices (always in bounds), masked accumulation: the loads
       // of all terms are in flight together
@@ -4715,6 +4782,13 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
         DY[rh] = dyh;
         DY[rh + 1] = dyb;
         DX[ncb + h] = xv - xo;
+      }
+      else
+      {
+        const double yhn = yh + dyh, ybn = yb + dyb;
+        const double etan = rho_s * zr - yhn;
+        const double rnn = (sig * xv - q) + bs * (rho_s * zs - ybn);
+        MRl[nr + h] = (etan * dn - rho_s * w * rnn) * deni;
       }
     }
   };
@@ -4835,7 +4909,12 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
   }
   // the chain pack of this factorisation (ends with a barrier)
   SegChain ch;
-  seg_chain_pack(c, sv, ch);
+  seg_chain_pack(c, sv, ch, !fac_kept);
+  if (tid == 0)  // (every thread read the stamps before that barrier)
+  {
+    c.s->qp_stamp |= 2;
+    c.s->fac_stamp = 1;
+  }
   int cbslot[CS];  // pack slot of each owned column's right-hand side
 #pragma unroll
   for (int u = 0; u < CS; ++u)
@@ -4849,6 +4928,7 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
   // (a global read-modify-write per lap would stall wave 0 inside the loop)
   long long* pf = (tid == 0) ? c.s->prof : nullptr;
   long long tq = pf ? clock64() : 0;
+  const long long lap37 = tq - t_in;
   long long lap8 = 0, lap9 = 0, lap10 = 0, lap11 = 0, lap15 = 0, lap16 = 0, lap17 = 0, lap18 = 0, lap34 = 0;
 #define SEG_LAP(acc)                  \
   if (pf)                             \
@@ -4874,7 +4954,7 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
         const double dn = adn[u], dp = adp[u], wn = awn[u], wp = awp[u], rr = arr[u];
         MRl[tid + kBlock * u] = (aeta[u] * dn * dp - rr * (wn * dp * arn[u] + wp * dn * arp[u])) * adeti[u];
       }
-    if (nh > 0)
+    if (nh > 0 && iter == 0)  // (later iterations: the previous hinge_e wrote MR)
     {
       if (pk_l)
         hinge_a(lds(HPK));
@@ -5001,6 +5081,7 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
     pf[34] += lap34;
     pf[17] += lap17;
     pf[18] += lap18;
+    pf[37] += lap37;
   }
   // residuals at the segment's last iterate (compute_residuals' quantities,
   // with its arithmetic order), from the state in registers: x of the
@@ -5131,7 +5212,7 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
       }
     for (int h = tid; h < nh; h += kBlock)
     {
-      const int rh = mb + 2 * h, col = ncb + h, t0 = static_cast<int>(HPK[12 * nh + h]);
+      const int rh = mb + 2 * h, col = ncb + h, t0 = static_cast<int>(HPK[10 * nh + h]);
       const double xh = HPK[4 * nh + h], wh = HPK[7 * nh + h], bsh = HPK[8 * nh + h];
       double ax = 0, ax1 = 0;
       for (int k = 0; k < D; ++k)
@@ -5169,7 +5250,10 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
     res->dr = v[10];
     res->q = v[11];
   }
-  // write back
+  // write back (the generic consumers read these arrays; the next segment of
+  // the QP reloads the column / CartPose owners' state from them, the hinge
+  // rows' state stays in the pack)
+  const long long t_wb = pf ? clock64() : 0;  // seg_writeback: from here to the return
 #pragma unroll
   for (int u = 0; u < CS; ++u)
     if (cact[u])
@@ -5218,6 +5302,8 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
   }
 #undef HP_
   BSYNC();
+  if (pf)
+    pf[38] += clock64() - t_wb;
 }
 
 __device__ void admm_iterations(Ctx& c, Solver& sv, int n_iter, Norms* res)
@@ -5440,6 +5526,9 @@ __device__ int qp_solve(Ctx& c, Solver& sv, bool pattern_equal)
     c.s->cur = 0;
     c.s->qp_status = ST_UNSOLVED;
     c.s->polish_status = 0;
+    // a new QP: other hinge rows, and plan_lds_dynamic may have moved the arrays
+    c.s->qp_stamp = 0;
+    c.s->fac_stamp = 0;
   }
   BSYNC();
   set_rho_vec(c);

@@ -32,6 +32,7 @@ EVAL_MAX_PRIMS = 1024  # THIP_EVAL_MAX_PRIMS
 TRACE_W = 16  # THIP_TRACE_W
 DEBUG_NO_SEGMENT, DEBUG_FORCE_WIDE, DEBUG_NO_BRANCH, DEBUG_STATIC_DISPATCH, DEBUG_GEN_BUILD = 1, 2, 4, 8, 16  # thip_debug_set_path flags
 DEBUG_MAIN_BUILD = 32
+DEBUG_SEG_REBUILD = 64  # the segment's packs rebuilt at every call (bitwise the same results)
 
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_CONTINUOUS, JOINT_PRISMATIC = 0, 1, 2, 3
 PRIM_SPHERE, PRIM_BOX, PRIM_CAPSULE = 0, 1, 2
