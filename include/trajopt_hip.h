@@ -589,6 +589,9 @@ int thip_debug_layout(thip_ctx* ctx, long long* doff, long long* ioff, long long
 #define THIP_DEBUG_SEG_REBUILD 64     /* the ADMM segment rebuilds its chain pack and hinge-row set-up at every
                                          call instead of once per factorisation / per QP (bitwise the same
                                          results) */
+#define THIP_DEBUG_SEG_RETURN 128     /* the ADMM segment returns to qp_solve() at every termination check and
+                                         check_termination ignores the segment's third infeasibility tests, as
+                                         before round 8 (bitwise the same results) */
 int thip_debug_set_path(int flags);
 int thip_debug_workspace(thip_ctx* ctx, double* dws, int* iws);
 /* The solve layout a context chose (diagnostic): out[0] block-solve branches

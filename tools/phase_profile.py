@@ -58,4 +58,4 @@ for b in np.argsort(-pf[:, 14])[:4]:
           f"mean hinge rows {nh_avg[b]:.0f}, contact rows {res[b].n_contact_rows}\n    {parts}")
 print(f"mean hinge rows per ADMM iteration (all): {nh_avg.mean():.1f}, max {nh_avg.max():.0f}")
 print(f"per QP: full primal-infeasibility checks {pf[:, 27].sum() / qps.sum():.2f}, "
-      f"full dual-infeasibility checks {pf[:, 28].sum() / qps.sum():.2f}, factorisations {pf[:, 29].sum() / qps.sum():.2f}")
+      f"full dual-infeasibility checks {pf[:, 28].sum() / qps.sum():.2f}, factorisations {pf[:, 29].sum() / qps.sum():.2f}, segment entries {pf[:, 39].sum() / qps.sum():.2f}")

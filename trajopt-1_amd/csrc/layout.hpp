@@ -230,6 +230,10 @@ struct Layout
   // diagnostic (THIP_DEBUG_SEG_REBUILD): the segment and factor() rebuild their
   // per-QP / per-factorisation packs at every call (Ctl's stamps read as stale)
   int seg_rebuild;
+  // diagnostic (THIP_DEBUG_SEG_RETURN): the segment returns at every termination
+  // check and its third infeasibility tests are not used (every certificate
+  // that passes the first two goes to the full function)
+  int seg_return;
   // middle block of the twisted block factorisation (N / 2)
   int tw_mid;
   // Branches of the block solve.  A kinematic tree whose terms never touch two

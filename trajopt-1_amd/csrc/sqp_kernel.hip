@@ -234,7 +234,8 @@ __device__ __forceinline__ const gbl_f64* gbl(const double* p) { return (const g
 // chain, 11 aux back-substitution (segment: phase E), 12 qp_solve, 13 sqp
 // total, 14 sqp total (wall clock, 100 MHz ticks), 15 segment phase B
 // (rhs + Linv b), 16 segment phase C2 (Linv^T y + middle block), 37 segment
-// set-up (entry to the first iteration), 38 segment write-back.
+// set-up (entry to the first iteration), 38 segment write-back, 39 segment
+// entries (a count).
 struct ProfScope
 {
   long long* p;
@@ -3923,6 +3924,11 @@ struct Norms
   // max |E dy|, sum u (dy)+ + l (dy)- over the clipped delta y, max |D dx|, q'dx
   int inf_ready;
   double ndy, lhs, ndx, qdx;
+  // their third tests, with inf_ready: pdx = max |D^-1 P dx| (always), and
+  // atdy = max |D^-1 A' dy| when aty_ready (the segment computes it only when
+  // the first two primal tests pass)
+  int aty_ready;
+  double pdx, atdy;
 };
 
 __device__ void compute_residuals(Ctx& c, const double* x, const double* z, const double* y, Norms& nm)
@@ -3965,6 +3971,7 @@ __device__ void compute_residuals(Ctx& c, const double* x, const double* z, cons
   }
   block_max<12>(c, v);
   nm.inf_ready = 0;
+  nm.aty_ready = 0;
   nm.prim_res = (c.m() > 0) ? v[0] : 0.0;
   nm.zE = v[1];
   nm.axE = v[2];
@@ -4061,11 +4068,22 @@ __device__ bool is_dual_infeasible(Ctx& c, double eps)
   return bad[0] == 0.0;
 }
 
-// check_termination; sets c.s->qp_status when it fires
-__device__ bool check_termination(Ctx& c, const Norms& nm, bool approx)
+// The scalar part of check_termination: a pure function of the norms, the
+// settings, the problem's scalars (row count, cost scaling c and 1 / c) and
+// approx.  prim_ok / dual_ok: the residual is inside its tolerance; need_pinf /
+// need_dinf: the certificate passed every test the norms hold (or they hold
+// none), so the full function has to decide.  use3 = false ignores the third
+// tests (Layout::seg_return).  qp_solve() and the resident ADMM segment both
+// decide with this one copy.
+struct TermDec
 {
-  PROF(2);
-  const thip_osqp_settings& os = c.d->osqp;
+  bool prim_ok, dual_ok, need_pinf, need_dinf;
+  __device__ __forceinline__ bool solved() const { return prim_ok && dual_ok; }
+  __device__ __forceinline__ bool carry_on() const { return !solved() && !need_pinf && !need_dinf; }
+};
+__device__ __forceinline__ TermDec term_decide(const Norms& nm, const thip_osqp_settings& os, bool approx, int m,
+                                               double cs, double cinv, bool use3)
+{
   double ea = os.eps_abs, er = os.eps_rel, epi = os.eps_prim_inf, edi = os.eps_dual_inf;
   if (approx)
   {
@@ -4074,28 +4092,74 @@ __device__ bool check_termination(Ctx& c, const Norms& nm, bool approx)
     epi *= 10;
     edi *= 10;
   }
-  bool prim_ok = false, dual_ok = false, pinf = false, dinf = false;
-  if (c.m() == 0)
-    prim_ok = true;
+  TermDec d{ false, false, false, false };
+  if (m == 0)
+    d.prim_ok = true;
   else
   {
     const double eps_prim = ea + er * fmax(nm.zE, nm.axE);
     if (nm.prim_res < eps_prim)
-      prim_ok = true;
+      d.prim_ok = true;
     else if (nm.inf_ready && (!(nm.ndy > kDivTol) || !(nm.lhs < epi * nm.ndy)))
-      pinf = false;  // is_primal_infeasible's first two tests, from the segment
+      d.need_pinf = false;  // is_primal_infeasible's first two tests, from the segment
+    else if (use3 && nm.inf_ready && nm.aty_ready && !(nm.atdy < epi * nm.ndy))
+      d.need_pinf = false;  // its third
     else
-      pinf = is_primal_infeasible(c, epi);
+      d.need_pinf = true;
   }
-  const double eps_dual = ea + er * (c.s->cinv * fmax(fmax(nm.qD, nm.atyD), nm.pxD));
+  const double eps_dual = ea + er * (cinv * fmax(fmax(nm.qD, nm.atyD), nm.pxD));
   if (nm.dual_res < eps_dual)
-    dual_ok = true;
-  else if (nm.inf_ready && (!(nm.ndx > kDivTol) || !(nm.qdx < c.s->c * edi * nm.ndx)))
-    dinf = false;  // is_dual_infeasible's first two tests, from the segment
+    d.dual_ok = true;
+  else if (nm.inf_ready && (!(nm.ndx > kDivTol) || !(nm.qdx < cs * edi * nm.ndx)))
+    d.need_dinf = false;  // is_dual_infeasible's first two tests, from the segment
+  else if (use3 && nm.inf_ready && !(nm.pdx < cs * edi * nm.ndx))
+    d.need_dinf = false;  // its third
   else
-    dinf = is_dual_infeasible(c, edi);
+    d.need_dinf = true;
+  return d;
+}
+
+// The ADMM loop's stops, shared by qp_solve() and the resident segment: the
+// next iteration >= it that checks termination or ends a rho interval (or
+// max_iter), whether a stop needs the residuals, whether it ends a rho
+// interval, and the rho update's tolerance band.
+__device__ __forceinline__ int admm_next_stop(const thip_osqp_settings& os, int interval, int it)
+{
+  const int ct = os.check_termination;
+  int stop = os.max_iter;
+  if (ct)
+    stop = min(stop, (it + ct - 1) / ct * ct);
+  if (os.adaptive_rho && interval)
+    stop = min(stop, (it + interval - 1) / interval * interval);
+  return stop;
+}
+__device__ __forceinline__ bool admm_stop_ends_rho(const thip_osqp_settings& os, int interval, int stop)
+{
+  return os.adaptive_rho && interval && (stop % interval == 0);
+}
+__device__ __forceinline__ bool admm_stop_wants_res(const thip_osqp_settings& os, int interval, int stop)
+{
+  return (os.check_termination && stop % os.check_termination == 0) || admm_stop_ends_rho(os, interval, stop);
+}
+__device__ __forceinline__ bool rho_outside_band(const thip_osqp_settings& os, double rn, double rho)
+{
+  return rn > rho * os.adaptive_rho_tolerance || rn < rho / os.adaptive_rho_tolerance;
+}
+__device__ double rho_estimate(Ctx& c, const Norms& nm);
+
+// check_termination; sets c.s->qp_status when it fires
+__device__ bool check_termination(Ctx& c, const Norms& nm, bool approx)
+{
+  PROF(2);
+  const thip_osqp_settings& os = c.d->osqp;
+  const double epi = approx ? os.eps_prim_inf * 10 : os.eps_prim_inf;
+  const double edi = approx ? os.eps_dual_inf * 10 : os.eps_dual_inf;
+  const TermDec d = term_decide(nm, os, approx, c.m(), c.s->c, c.s->cinv, !c.L.seg_return);
+  // only the full functions may declare infeasibility
+  const bool pinf = d.need_pinf ? is_primal_infeasible(c, epi) : false;
+  const bool dinf = d.need_dinf ? is_dual_infeasible(c, edi) : false;
   int st = 0;
-  if (prim_ok && dual_ok)
+  if (d.solved())
     st = approx ? ST_SOLVED_INACC : ST_SOLVED;
   else if (pinf)
     st = approx ? ST_PINF_INACC : ST_PINF;
@@ -4594,8 +4658,18 @@ __device__ __forceinline__ void admm_row_update(double& z, double& y, double& dy
   z = zr;
 }
 
+// Runs the ADMM iterations it .. stop (stop = admm_next_stop(it)) and, when the
+// stop wants them, the residuals of the last iterate into nm.  Then the
+// segment decides what qp_solve() would decide from nm (term_decide, the rho
+// band): when that is "carry on with the same rho" -- status 0, no full
+// infeasibility check needed, no rho update, iterations left -- it goes on to
+// the next stop in place, with its state in registers and without write-back
+// or set-up.  Otherwise it writes back and returns.  Returns the iterations
+// executed; nm is that of the last stop, and qp_solve() re-evaluates it through
+// the same functions, so it takes the branch the segment left for.
+// Layout::seg_return: return at the first stop, as every call did before.
 template <int CS, int AS>
-__device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
+__device__ int admm_segment(Ctx& c, Solver& sv, int it, int stop, int interval, Norms& nm)
 {
   PROF(0);
   const long long t_in = (c.tid == 0 && c.s->prof) ? clock64() : 0;  // seg_setup: from here to the loop
@@ -4937,137 +5011,428 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
     acc += tn - tq;                   \
     tq = tn;                          \
   }
-  for (int iter = 0; iter < n_iter; ++iter)
+  if (pf)
+    pf[39] += 1;  // segment entries (diagnostic count)
+  int done = 0;
+  for (;;)  // one pass per stop
   {
-    // A: CartPose rows -> MR (aux block eliminated, see reduced_solve)
+    const int n_iter = stop - it + 1;
+    Norms* const res = admm_stop_wants_res(os, interval, stop) ? &nm : nullptr;
+    for (int iter = 0; iter < n_iter; ++iter)
+    {
+      // A: CartPose rows -> MR (aux block eliminated, see reduced_solve)
 #pragma unroll
-    for (int u = 0; u < AS; ++u)
-      if (aact[u])
-      {
-        const double bxn = sig * axn[u] - aqn[u];
-        const double bxp = sig * axp[u] - aqp[u];
-        const double ebn = arbn[u] * azbn[u] - aybn[u];
-        const double ebp = arbp[u] * azbp[u] - aybp[u];
-        aeta[u] = arr[u] * azr[u] - ayr[u];
-        arn[u] = bxn + absn[u] * ebn;
-        arp[u] = bxp + absp[u] * ebp;
-        const double dn = adn[u], dp = adp[u], wn = awn[u], wp = awp[u], rr = arr[u];
-        MRl[tid + kBlock * u] = (aeta[u] * dn * dp - rr * (wn * dp * arn[u] + wp * dn * arp[u])) * adeti[u];
-      }
-    if (nh > 0 && iter == 0)  // (later iterations: the previous hinge_e wrote MR)
-    {
-      if (pk_l)
-        hinge_a(lds(HPK));
-      else
-        hinge_a(gbl(HPK));
-    }
-    BSYNC();
-    SEG_LAP(lap8);
-    if (nh > 0)
-    {
-      if (hct_l)
-        hinge_gather_seg(lds(static_cast<const double*>(HCT)));
-      else
-        hinge_gather_seg(gbl(static_cast<const double*>(HCT)));
-      BSYNC();
-    }
-    SEG_LAP(lap17);
-    // B: waypoint right-hand sides b -> YV
-#pragma unroll
-    for (int u = 0; u < CS; ++u)
-    {
-      if (cact[u])
-      {
-        const double bx = sig * cx[u] - cq[u];
-        const double eb = crb[u] * czb[u] - cyb[u];
-        double b = bx + cbs[u] * eb;
-        if (cfr[u] >= 0)
+      for (int u = 0; u < AS; ++u)
+        if (aact[u])
         {
-          const double ef = crf[u] * czf[u] - cyf[u];
-          b += cfs[u] * ef;
+          const double bxn = sig * axn[u] - aqn[u];
+          const double bxp = sig * axp[u] - aqp[u];
+          const double ebn = arbn[u] * azbn[u] - aybn[u];
+          const double ebp = arbp[u] * azbp[u] - aybp[u];
+          aeta[u] = arr[u] * azr[u] - ayr[u];
+          arn[u] = bxn + absn[u] * ebn;
+          arp[u] = bxp + absp[u] * ebp;
+          const double dn = adn[u], dp = adp[u], wn = awn[u], wp = awp[u], rr = arr[u];
+          MRl[tid + kBlock * u] = (aeta[u] * dn * dp - rr * (wn * dp * arn[u] + wp * dn * arp[u])) * adeti[u];
+        }
+      if (nh > 0 && iter == 0)  // (later iterations: the previous hinge_e wrote MR)
+      {
+        if (pk_l)
+          hinge_a(lds(HPK));
+        else
+          hinge_a(gbl(HPK));
+      }
+      BSYNC();
+      SEG_LAP(lap8);
+      if (nh > 0)
+      {
+        if (hct_l)
+          hinge_gather_seg(lds(static_cast<const double*>(HCT)));
+        else
+          hinge_gather_seg(gbl(static_cast<const double*>(HCT)));
+        BSYNC();
+      }
+      SEG_LAP(lap17);
+      // B: waypoint right-hand sides b -> YV
+#pragma unroll
+      for (int u = 0; u < CS; ++u)
+      {
+        if (cact[u])
+        {
+          const double bx = sig * cx[u] - cq[u];
+          const double eb = crb[u] * czb[u] - cyb[u];
+          double b = bx + cbs[u] * eb;
+          if (cfr[u] >= 0)
+          {
+            const double ef = crf[u] * czf[u] - cyf[u];
+            b += cfs[u] * ef;
+          }
+#pragma unroll
+          for (int p = 0; p < kMaxStepRows; ++p)
+            if (p < cnrow[u])
+              b += cgs[u][p] * MRl[crow[u][p]];
+          if (nh > 0)
+          {
+            const int j = (tid + kBlock * u) & 7;
+            for (int q = chp1[u]; q < chp2[u]; ++q)
+              b += PARTl[q * 16 + j];
+            for (int q = chp0[u]; q < chp1[u]; ++q)
+              b += PARTl[q * 16 + D + j];
+          }
+          CPKl[cbslot[u]] = b;
+        }
+      }
+      BSYNC();
+      SEG_LAP(lap15);
+      // x~ = K^-1 b into CV: forward halves, middle + backward halves
+      seg_chain_solve(ch, lap9, lap10, pf, tq, lap16, lap34);
+      // E: back-substitution, z~ = A x~, relaxed updates
+      const bool last = (iter == n_iter - 1);
+#pragma unroll
+      for (int u = 0; u < CS; ++u)
+        if (cact[u])
+        {
+          const double xt = lds(CV)[ccol[u]];
+          admm_row_update(czb[u], cyb[u], cdyb[u], cbs[u] * xt, crb[u], crbi[u], clb[u], cub[u], al);
+          if (cfr[u] >= 0)
+            admm_row_update(czf[u], cyf[u], cdyf[u], cfs[u] * xt, crf[u], crfi[u], clf[u], cuf[u], al);
+          const double xv = al * xt + (1.0 - al) * cx[u];
+          cdx[u] = xv - cx[u];
+          cx[u] = xv;
         }
 #pragma unroll
-        for (int p = 0; p < kMaxStepRows; ++p)
-          if (p < cnrow[u])
-            b += cgs[u][p] * MRl[crow[u][p]];
+      for (int u = 0; u < AS; ++u)
+        if (aact[u])
+        {
+          const int t = at[u];
+          double g0 = 0, g1 = 0;
+#pragma unroll
+          for (int j = 0; j < kOct; ++j)
+          {
+            const double xv = lds(CV)[t * D + ((j < D) ? j : D - 1)];
+            const double xm = xv * ((j < D) ? 1.0 : 0.0);  // a 0/1 multiplier, not a select
+            if (j & 1)
+              g1 += ags[u][j] * xm;
+            else
+              g0 += ags[u][j] * xm;
+          }
+          const double g = g0 + g1;
+          const double dn = adn[u], dp = adp[u], wn = awn[u], wp = awp[u], rr = arr[u];
+          const double rn = arn[u], rp = arp[u];
+          const double deti = adeti[u];
+          const double cross = wp * rn - wn * rp;
+          const double h = aeta[u] - rr * g;
+          const double an = (dp * rn + rr * wp * cross + wn * dp * h) * deti;
+          const double ap = (dn * rp - rr * wn * cross + wp * dn * h) * deti;
+          double zt = g;
+          zt += wn * an + wp * ap;
+          admm_row_update(azr[u], ayr[u], adyr[u], zt, rr, arri[u], alr[u], aur[u], al);
+          admm_row_update(azbn[u], aybn[u], adybn[u], absn[u] * an, arbn[u], arbni[u], albn[u], aubn[u], al);
+          admm_row_update(azbp[u], aybp[u], adybp[u], absp[u] * ap, arbp[u], arbpi[u], albp[u], aubp[u], al);
+          const double xvn = al * an + (1.0 - al) * axn[u];
+          const double xvp = al * ap + (1.0 - al) * axp[u];
+          adxn[u] = xvn - axn[u];
+          adxp[u] = xvp - axp[u];
+          axn[u] = xvn;
+          axp[u] = xvp;
+        }
+      SEG_LAP(lap11);
+      if (nh > 0)
+      {
+        if (pk_l && hct_l)
+          hinge_e(lds(HPK), lds(static_cast<const double*>(HCT)), last);
+        else if (pk_l)
+          hinge_e(lds(HPK), gbl(static_cast<const double*>(HCT)), last);
+        else if (hct_l)
+          hinge_e(gbl(HPK), lds(static_cast<const double*>(HCT)), last);
+        else
+          hinge_e(gbl(HPK), gbl(static_cast<const double*>(HCT)), last);
+      }
+      SEG_LAP(lap18);
+    }
+    // residuals at the segment's last iterate (compute_residuals' quantities,
+    // with its arithmetic order), from the state in registers: x of the
+    // waypoint columns into YV and y of the CartPose / hinge rows into MR, one
+    // barrier, the hinge share of A'y as chunk sums (phase B's gather on y),
+    // then every owner's rows (A x - z) and columns (q + P x + A'y)
+    if (res)
+    {
+      PROF(1);
+#pragma unroll
+      for (int u = 0; u < CS; ++u)
+        if (cact[u])
+        {
+          lds(YV)[ccol[u]] = cx[u];
+          // delta x for the neighbours' (P dx)_col, in the column's right-hand-side
+          // slot of the chain pack: the last solve has read it (behind its
+          // closing barrier) and phase B stores every active slot again before
+          // the next solve reads any
+          CPKl[cbslot[u]] = cdx[u];
+        }
+#pragma unroll
+      for (int u = 0; u < AS; ++u)
+        if (aact[u])
+          MRl[tid + kBlock * u] = ayr[u];
+      for (int h = tid; h < nh; h += kBlock)
+        MRl[nr + h] = HPK[2 * nh + h];
+      BSYNC();
+      if (nh > 0)
+      {
+        if (hct_l)
+          hinge_gather_seg(lds(static_cast<const double*>(HCT)));
+        else
+          hinge_gather_seg(gbl(static_cast<const double*>(HCT)));
+        BSYNC();
+      }
+      const double *E = c.a(A_E), *DS = c.a(A_DS), *PD = c.a(A_PD), *PO = c.a(A_PO);
+      // v[12] = max |E dy| and v[13] = max |D dx| over the clipped delta y / delta x
+      // of the last iteration (is_primal_infeasible / is_dual_infeasible)
+      // v[14] = max |D^-1 P dx| (is_dual_infeasible's third test)
+      double v[15] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+      double lhs = 0.0, qdx = 0.0;
+      auto inf_row = [&](double dy, double lo, double up, double e) {
+        if (up > kInf * kMinScal)
+          dy = (lo < -kInf * kMinScal) ? 0.0 : fmin(dy, 0.0);
+        else if (lo < -kInf * kMinScal)
+          dy = fmax(dy, 0.0);
+        v[12] = fmax(v[12], fabs(e * dy));
+        lhs += up * fmax(dy, 0.0) + lo * fmin(dy, 0.0);
+      };
+      auto inf_col = [&](double dx, double q, double ds) {
+        v[13] = fmax(v[13], fabs(ds * dx));
+        qdx += q * dx;
+      };
+      auto row_terms = [&](double ax, double z, double e) {
+        const double pr = ax - z;
+        const double einv = 1.0 / e;
+        v[0] = fmax(v[0], fabs(einv * pr));
+        v[1] = fmax(v[1], fabs(einv * z));
+        v[2] = fmax(v[2], fabs(einv * ax));
+        v[3] = fmax(v[3], fabs(pr));
+        v[4] = fmax(v[4], fabs(z));
+        v[5] = fmax(v[5], fabs(ax));
+      };
+      auto col_terms = [&](double q, double px, double aty, double ds) {
+        const double dr = q + px + aty;
+        const double dinv = 1.0 / ds;
+        v[6] = fmax(v[6], fabs(dinv * dr));
+        v[7] = fmax(v[7], fabs(dinv * q));
+        v[8] = fmax(v[8], fabs(dinv * aty));
+        v[9] = fmax(v[9], fabs(dinv * px));
+        v[10] = fmax(v[10], fabs(dr));
+        v[11] = fmax(v[11], fmax(fabs(q), fmax(fabs(aty), fabs(px))));
+      };
+#pragma unroll
+      for (int u = 0; u < CS; ++u)
+        if (cact[u])
+        {
+          const int col = ccol[u], br = nr + col, t = col / D;
+          const double eb = E[br], ds = DS[col];
+          row_terms(cbs[u] * cx[u], czb[u], eb);
+          inf_row(cdyb[u], clb[u], cub[u], eb);
+          inf_col(cdx[u], cq[u], ds);
+          if (cfr[u] >= 0)
+          {
+            const double ef = E[cfr[u]];
+            row_terms(cfs[u] * cx[u], czf[u], ef);
+            inf_row(cdyf[u], clf[u], cuf[u], ef);
+          }
+          // col_px
+          double px = PD[col] * cx[u];
+          if (t < N - 1)
+            px += PO[col] * lds(YV)[col + D];
+          if (t > 0)
+            px += PO[col - D] * lds(YV)[col - D];
+          // col_px of delta x (the CartPose and hinge columns contribute 0)
+          {
+            const int i = col - t * D;
+            double pdx = PD[col] * cdx[u];
+            if (t < N - 1)
+              pdx += PO[col] * CPKl[seg_b_slot(t + 1, i, L.tw_mid)];
+            if (t > 0)
+              pdx += PO[col - D] * CPKl[seg_b_slot(t - 1, i, L.tw_mid)];
+            v[14] = fmax(v[14], fabs((1.0 / ds) * pdx));
+          }
+          // col_aty (chunked)
+          double aty = cbs[u] * cyb[u];
+          if (cfr[u] >= 0)
+            aty += cfs[u] * cyf[u];
+#pragma unroll
+          for (int p = 0; p < kMaxStepRows; ++p)
+            if (p < cnrow[u])
+              aty += cgs[u][p] * MRl[crow[u][p]];
+          if (nh > 0)
+          {
+            const int j = (tid + kBlock * u) & 7;
+            for (int q = chp1[u]; q < chp2[u]; ++q)
+              aty += PARTl[q * 16 + j];
+            for (int q = chp0[u]; q < chp1[u]; ++q)
+              aty += PARTl[q * 16 + D + j];
+          }
+          col_terms(cq[u], px, aty, ds);
+        }
+#pragma unroll
+      for (int u = 0; u < AS; ++u)
+        if (aact[u])
+        {
+          const int a = tid + kBlock * u;
+          const int r = nfr + a, ca = nx + 2 * a, brn = nr + ca, brp = brn + 1;
+          const int t = at[u];
+          double ax = 0;
+#pragma unroll
+          for (int j = 0; j < kOct; ++j)  // 0/1 multiplier, not a guard (see masked_dot)
+            ax += ags[u][j] * (lds(YV)[t * D + min(j, D - 1)] * ((j < D) ? 1.0 : 0.0));
+          ax += awn[u] * axn[u] + awp[u] * axp[u];
+          const double er = E[r], en = E[brn], ep = E[brp], dn = DS[ca], dp = DS[ca + 1];
+          row_terms(ax, azr[u], er);
+          row_terms(absn[u] * axn[u], azbn[u], en);
+          row_terms(absp[u] * axp[u], azbp[u], ep);
+          col_terms(aqn[u], 0.0, absn[u] * aybn[u] + awn[u] * ayr[u], dn);
+          col_terms(aqp[u], 0.0, absp[u] * aybp[u] + awp[u] * ayr[u], dp);
+          inf_row(adyr[u], alr[u], aur[u], er);
+          inf_row(adybn[u], albn[u], aubn[u], en);
+          inf_row(adybp[u], albp[u], aubp[u], ep);
+          inf_col(adxn[u], aqn[u], dn);
+          inf_col(adxp[u], aqp[u], dp);
+        }
+      for (int h = tid; h < nh; h += kBlock)
+      {
+        const int rh = mb + 2 * h, col = ncb + h, t0 = static_cast<int>(HPK[10 * nh + h]);
+        const double xh = HPK[4 * nh + h], wh = HPK[7 * nh + h], bsh = HPK[8 * nh + h];
+        double ax = 0, ax1 = 0;
+        for (int k = 0; k < D; ++k)
+        {
+          ax += HC[h * 2 * D + k] * lds(YV)[t0 + k];
+          ax1 += HC[h * 2 * D + D + k] * lds(YV)[t0 + D + k];
+        }
+        ax = ax + ax1 + wh * xh;  // row_ax: hinge_dot + w h
+        const double e0 = E[rh], e1 = E[rh + 1], ds = DS[col];
+        row_terms(ax, HPK[h], e0);
+        row_terms(bsh * xh, HPK[nh + h], e1);
+        col_terms(HPK[9 * nh + h], 0.0, bsh * HPK[3 * nh + h] + wh * HPK[2 * nh + h], ds);
+        // (DY / DX of the last iteration, written by hinge_e)
+        inf_row(DY[rh], Lo[rh], Up[rh], e0);
+        inf_row(DY[rh + 1], Lo[rh + 1], Up[rh + 1], e1);
+        inf_col(DX[col], HPK[9 * nh + h], ds);
+      }
+      block_max<15>(c, v);
+      block_sum2(c, lhs, qdx);
+      // is_primal_infeasible's third test, max |D^-1 A' dy| over the clipped delta
+      // y, when its first two pass (the whole workgroup takes the same branch:
+      // the operands are reduction results): the clipped dy of the CartPose and
+      // hinge rows into MR (read by nobody past the reductions' barriers), the
+      // hinge rows' share as chunk sums, then every owner's columns in col_aty's
+      // order
+      res->aty_ready = 0;
+      if ((v[12] > kDivTol) && (lhs < os.eps_prim_inf * v[12]) && !L.seg_return)
+      {
+        auto clip_dy = [&](double dy, double lo, double up) {
+          if (up > kInf * kMinScal)
+            dy = (lo < -kInf * kMinScal) ? 0.0 : fmin(dy, 0.0);
+          else if (lo < -kInf * kMinScal)
+            dy = fmax(dy, 0.0);
+          return dy;
+        };
+        double av[1] = { 0 };
+        double ady[AS];
+#pragma unroll
+        for (int u = 0; u < AS; ++u)
+          if (aact[u])
+          {
+            ady[u] = clip_dy(adyr[u], alr[u], aur[u]);
+            MRl[tid + kBlock * u] = ady[u];
+          }
+        for (int h = tid; h < nh; h += kBlock)
+        {
+          const int rh = mb + 2 * h;
+          MRl[nr + h] = clip_dy(DY[rh], Lo[rh], Up[rh]);
+        }
+        BSYNC();
         if (nh > 0)
         {
-          const int j = (tid + kBlock * u) & 7;
-          for (int q = chp1[u]; q < chp2[u]; ++q)
-            b += PARTl[q * 16 + j];
-          for (int q = chp0[u]; q < chp1[u]; ++q)
-            b += PARTl[q * 16 + D + j];
-        }
-        CPKl[cbslot[u]] = b;
-      }
-    }
-    BSYNC();
-    SEG_LAP(lap15);
-    // x~ = K^-1 b into CV: forward halves, middle + backward halves
-    seg_chain_solve(ch, lap9, lap10, pf, tq, lap16, lap34);
-    // E: back-substitution, z~ = A x~, relaxed updates
-    const bool last = (iter == n_iter - 1);
-#pragma unroll
-    for (int u = 0; u < CS; ++u)
-      if (cact[u])
-      {
-        const double xt = lds(CV)[ccol[u]];
-        admm_row_update(czb[u], cyb[u], cdyb[u], cbs[u] * xt, crb[u], crbi[u], clb[u], cub[u], al);
-        if (cfr[u] >= 0)
-          admm_row_update(czf[u], cyf[u], cdyf[u], cfs[u] * xt, crf[u], crfi[u], clf[u], cuf[u], al);
-        const double xv = al * xt + (1.0 - al) * cx[u];
-        cdx[u] = xv - cx[u];
-        cx[u] = xv;
-      }
-#pragma unroll
-    for (int u = 0; u < AS; ++u)
-      if (aact[u])
-      {
-        const int t = at[u];
-        double g0 = 0, g1 = 0;
-#pragma unroll
-        for (int j = 0; j < kOct; ++j)
-        {
-          const double xv = lds(CV)[t * D + ((j < D) ? j : D - 1)];
-          const double xm = xv * ((j < D) ? 1.0 : 0.0);  // a 0/1 multiplier, not a select
-          if (j & 1)
-            g1 += ags[u][j] * xm;
+          if (hct_l)
+            hinge_gather_seg(lds(static_cast<const double*>(HCT)));
           else
-            g0 += ags[u][j] * xm;
+            hinge_gather_seg(gbl(static_cast<const double*>(HCT)));
+          BSYNC();
         }
-        const double g = g0 + g1;
-        const double dn = adn[u], dp = adp[u], wn = awn[u], wp = awp[u], rr = arr[u];
-        const double rn = arn[u], rp = arp[u];
-        const double deti = adeti[u];
-        const double cross = wp * rn - wn * rp;
-        const double h = aeta[u] - rr * g;
-        const double an = (dp * rn + rr * wp * cross + wn * dp * h) * deti;
-        const double ap = (dn * rp - rr * wn * cross + wp * dn * h) * deti;
-        double zt = g;
-        zt += wn * an + wp * ap;
-        admm_row_update(azr[u], ayr[u], adyr[u], zt, rr, arri[u], alr[u], aur[u], al);
-        admm_row_update(azbn[u], aybn[u], adybn[u], absn[u] * an, arbn[u], arbni[u], albn[u], aubn[u], al);
-        admm_row_update(azbp[u], aybp[u], adybp[u], absp[u] * ap, arbp[u], arbpi[u], albp[u], aubp[u], al);
-        const double xvn = al * an + (1.0 - al) * axn[u];
-        const double xvp = al * ap + (1.0 - al) * axp[u];
-        adxn[u] = xvn - axn[u];
-        adxp[u] = xvp - axp[u];
-        axn[u] = xvn;
-        axp[u] = xvp;
+#pragma unroll
+        for (int u = 0; u < CS; ++u)
+          if (cact[u])
+          {
+            double aty = cbs[u] * clip_dy(cdyb[u], clb[u], cub[u]);
+            if (cfr[u] >= 0)
+              aty += cfs[u] * clip_dy(cdyf[u], clf[u], cuf[u]);
+#pragma unroll
+            for (int p = 0; p < kMaxStepRows; ++p)
+              if (p < cnrow[u])
+                aty += cgs[u][p] * MRl[crow[u][p]];
+            if (nh > 0)
+            {
+              const int j = (tid + kBlock * u) & 7;
+              for (int q = chp1[u]; q < chp2[u]; ++q)
+                aty += PARTl[q * 16 + j];
+              for (int q = chp0[u]; q < chp1[u]; ++q)
+                aty += PARTl[q * 16 + D + j];
+            }
+            av[0] = fmax(av[0], fabs((1.0 / DS[ccol[u]]) * aty));
+          }
+#pragma unroll
+        for (int u = 0; u < AS; ++u)
+          if (aact[u])
+          {
+            const int ca = nx + 2 * (tid + kBlock * u);
+            const double atn = absn[u] * clip_dy(adybn[u], albn[u], aubn[u]) + awn[u] * ady[u];
+            const double atp = absp[u] * clip_dy(adybp[u], albp[u], aubp[u]) + awp[u] * ady[u];
+            av[0] = fmax(av[0], fmax(fabs((1.0 / DS[ca]) * atn), fabs((1.0 / DS[ca + 1]) * atp)));
+          }
+        for (int h = tid; h < nh; h += kBlock)
+        {
+          const int rh = mb + 2 * h, col = ncb + h;
+          const double aty = HPK[8 * nh + h] * clip_dy(DY[rh + 1], Lo[rh + 1], Up[rh + 1]) +
+                             HPK[7 * nh + h] * clip_dy(DY[rh], Lo[rh], Up[rh]);
+          av[0] = fmax(av[0], fabs((1.0 / DS[col]) * aty));
+        }
+        block_max<1>(c, av);
+        res->aty_ready = 1;
+        res->atdy = av[0];
       }
-    SEG_LAP(lap11);
-    if (nh > 0)
-    {
-      if (pk_l && hct_l)
-        hinge_e(lds(HPK), lds(static_cast<const double*>(HCT)), last);
-      else if (pk_l)
-        hinge_e(lds(HPK), gbl(static_cast<const double*>(HCT)), last);
-      else if (hct_l)
-        hinge_e(gbl(HPK), lds(static_cast<const double*>(HCT)), last);
-      else
-        hinge_e(gbl(HPK), gbl(static_cast<const double*>(HCT)), last);
+      res->pdx = v[14];
+      res->inf_ready = 1;
+      res->ndy = v[12];
+      res->lhs = lhs;
+      res->ndx = v[13];
+      res->qdx = qdx;
+      res->prim_res = (c.m() > 0) ? v[0] : 0.0;
+      res->zE = v[1];
+      res->axE = v[2];
+      res->pr = v[3];
+      res->z = v[4];
+      res->ax = v[5];
+      res->dual_res = c.s->cinv * v[6];
+      res->qD = v[7];
+      res->atyD = v[8];
+      res->pxD = v[9];
+      res->dr = v[10];
+      res->q = v[11];
     }
-    SEG_LAP(lap18);
+    done += n_iter;
+    // Stay resident?  Every operand is a reduction result or a workgroup
+    // scalar, so the whole workgroup takes the same branch.  While resident, the
+    // column / CartPose owners' XA, Z, Y, DX, DY in memory are stale; nothing
+    // reads them before the write-back below.  The next pass runs the stand-alone
+    // hinge_a (this pass's last iteration wrote no MR).
+    if (!res || L.seg_return || stop >= os.max_iter)
+      break;
+    if (os.check_termination && stop % os.check_termination == 0 &&
+        !term_decide(nm, os, false, c.m(), c.s->c, c.s->cinv, true).carry_on())
+      break;
+    if (admm_stop_ends_rho(os, interval, stop) && rho_outside_band(os, rho_estimate(c, nm), rho_s))
+      break;
+    it = stop + 1;
+    stop = admm_next_stop(os, interval, it);
+    if (pf)
+      tq = clock64();  // (the epilogue is slot 1's, not the next phase A lap's)
   }
 #undef SEG_LAP
   if (pf)
@@ -5082,173 +5447,6 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
     pf[17] += lap17;
     pf[18] += lap18;
     pf[37] += lap37;
-  }
-  // residuals at the segment's last iterate (compute_residuals' quantities,
-  // with its arithmetic order), from the state in registers: x of the
-  // waypoint columns into YV and y of the CartPose / hinge rows into MR, one
-  // barrier, the hinge share of A'y as chunk sums (phase B's gather on y),
-  // then every owner's rows (A x - z) and columns (q + P x + A'y)
-  if (res)
-  {
-    PROF(1);
-#pragma unroll
-    for (int u = 0; u < CS; ++u)
-      if (cact[u])
-        lds(YV)[ccol[u]] = cx[u];
-#pragma unroll
-    for (int u = 0; u < AS; ++u)
-      if (aact[u])
-        MRl[tid + kBlock * u] = ayr[u];
-    for (int h = tid; h < nh; h += kBlock)
-      MRl[nr + h] = HPK[2 * nh + h];
-    BSYNC();
-    if (nh > 0)
-    {
-      if (hct_l)
-        hinge_gather_seg(lds(static_cast<const double*>(HCT)));
-      else
-        hinge_gather_seg(gbl(static_cast<const double*>(HCT)));
-      BSYNC();
-    }
-    const double *E = c.a(A_E), *DS = c.a(A_DS), *PD = c.a(A_PD), *PO = c.a(A_PO);
-    // v[12] = max |E dy| and v[13] = max |D dx| over the clipped delta y / delta x
-    // of the last iteration (is_primal_infeasible / is_dual_infeasible)
-    double v[14] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-    double lhs = 0.0, qdx = 0.0;
-    auto inf_row = [&](double dy, double lo, double up, double e) {
-      if (up > kInf * kMinScal)
-        dy = (lo < -kInf * kMinScal) ? 0.0 : fmin(dy, 0.0);
-      else if (lo < -kInf * kMinScal)
-        dy = fmax(dy, 0.0);
-      v[12] = fmax(v[12], fabs(e * dy));
-      lhs += up * fmax(dy, 0.0) + lo * fmin(dy, 0.0);
-    };
-    auto inf_col = [&](double dx, double q, double ds) {
-      v[13] = fmax(v[13], fabs(ds * dx));
-      qdx += q * dx;
-    };
-    auto row_terms = [&](double ax, double z, double e) {
-      const double pr = ax - z;
-      const double einv = 1.0 / e;
-      v[0] = fmax(v[0], fabs(einv * pr));
-      v[1] = fmax(v[1], fabs(einv * z));
-      v[2] = fmax(v[2], fabs(einv * ax));
-      v[3] = fmax(v[3], fabs(pr));
-      v[4] = fmax(v[4], fabs(z));
-      v[5] = fmax(v[5], fabs(ax));
-    };
-    auto col_terms = [&](double q, double px, double aty, double ds) {
-      const double dr = q + px + aty;
-      const double dinv = 1.0 / ds;
-      v[6] = fmax(v[6], fabs(dinv * dr));
-      v[7] = fmax(v[7], fabs(dinv * q));
-      v[8] = fmax(v[8], fabs(dinv * aty));
-      v[9] = fmax(v[9], fabs(dinv * px));
-      v[10] = fmax(v[10], fabs(dr));
-      v[11] = fmax(v[11], fmax(fabs(q), fmax(fabs(aty), fabs(px))));
-    };
-#pragma unroll
-    for (int u = 0; u < CS; ++u)
-      if (cact[u])
-      {
-        const int col = ccol[u], br = nr + col, t = col / D;
-        const double eb = E[br], ds = DS[col];
-        row_terms(cbs[u] * cx[u], czb[u], eb);
-        inf_row(cdyb[u], clb[u], cub[u], eb);
-        inf_col(cdx[u], cq[u], ds);
-        if (cfr[u] >= 0)
-        {
-          const double ef = E[cfr[u]];
-          row_terms(cfs[u] * cx[u], czf[u], ef);
-          inf_row(cdyf[u], clf[u], cuf[u], ef);
-        }
-        // col_px
-        double px = PD[col] * cx[u];
-        if (t < N - 1)
-          px += PO[col] * lds(YV)[col + D];
-        if (t > 0)
-          px += PO[col - D] * lds(YV)[col - D];
-        // col_aty (chunked)
-        double aty = cbs[u] * cyb[u];
-        if (cfr[u] >= 0)
-          aty += cfs[u] * cyf[u];
-#pragma unroll
-        for (int p = 0; p < kMaxStepRows; ++p)
-          if (p < cnrow[u])
-            aty += cgs[u][p] * MRl[crow[u][p]];
-        if (nh > 0)
-        {
-          const int j = (tid + kBlock * u) & 7;
-          for (int q = chp1[u]; q < chp2[u]; ++q)
-            aty += PARTl[q * 16 + j];
-          for (int q = chp0[u]; q < chp1[u]; ++q)
-            aty += PARTl[q * 16 + D + j];
-        }
-        col_terms(cq[u], px, aty, ds);
-      }
-#pragma unroll
-    for (int u = 0; u < AS; ++u)
-      if (aact[u])
-      {
-        const int a = tid + kBlock * u;
-        const int r = nfr + a, ca = nx + 2 * a, brn = nr + ca, brp = brn + 1;
-        const int t = at[u];
-        double ax = 0;
-#pragma unroll
-        for (int j = 0; j < kOct; ++j)  // 0/1 multiplier, not a guard (see masked_dot)
-          ax += ags[u][j] * (lds(YV)[t * D + min(j, D - 1)] * ((j < D) ? 1.0 : 0.0));
-        ax += awn[u] * axn[u] + awp[u] * axp[u];
-        const double er = E[r], en = E[brn], ep = E[brp], dn = DS[ca], dp = DS[ca + 1];
-        row_terms(ax, azr[u], er);
-        row_terms(absn[u] * axn[u], azbn[u], en);
-        row_terms(absp[u] * axp[u], azbp[u], ep);
-        col_terms(aqn[u], 0.0, absn[u] * aybn[u] + awn[u] * ayr[u], dn);
-        col_terms(aqp[u], 0.0, absp[u] * aybp[u] + awp[u] * ayr[u], dp);
-        inf_row(adyr[u], alr[u], aur[u], er);
-        inf_row(adybn[u], albn[u], aubn[u], en);
-        inf_row(adybp[u], albp[u], aubp[u], ep);
-        inf_col(adxn[u], aqn[u], dn);
-        inf_col(adxp[u], aqp[u], dp);
-      }
-    for (int h = tid; h < nh; h += kBlock)
-    {
-      const int rh = mb + 2 * h, col = ncb + h, t0 = static_cast<int>(HPK[10 * nh + h]);
-      const double xh = HPK[4 * nh + h], wh = HPK[7 * nh + h], bsh = HPK[8 * nh + h];
-      double ax = 0, ax1 = 0;
-      for (int k = 0; k < D; ++k)
-      {
-        ax += HC[h * 2 * D + k] * lds(YV)[t0 + k];
-        ax1 += HC[h * 2 * D + D + k] * lds(YV)[t0 + D + k];
-      }
-      ax = ax + ax1 + wh * xh;  // row_ax: hinge_dot + w h
-      const double e0 = E[rh], e1 = E[rh + 1], ds = DS[col];
-      row_terms(ax, HPK[h], e0);
-      row_terms(bsh * xh, HPK[nh + h], e1);
-      col_terms(HPK[9 * nh + h], 0.0, bsh * HPK[3 * nh + h] + wh * HPK[2 * nh + h], ds);
-      // (DY / DX of the last iteration, written by hinge_e)
-      inf_row(DY[rh], Lo[rh], Up[rh], e0);
-      inf_row(DY[rh + 1], Lo[rh + 1], Up[rh + 1], e1);
-      inf_col(DX[col], HPK[9 * nh + h], ds);
-    }
-    block_max<14>(c, v);
-    block_sum2(c, lhs, qdx);
-    res->inf_ready = 1;
-    res->ndy = v[12];
-    res->lhs = lhs;
-    res->ndx = v[13];
-    res->qdx = qdx;
-    res->prim_res = (c.m() > 0) ? v[0] : 0.0;
-    res->zE = v[1];
-    res->axE = v[2];
-    res->pr = v[3];
-    res->z = v[4];
-    res->ax = v[5];
-    res->dual_res = c.s->cinv * v[6];
-    res->qD = v[7];
-    res->atyD = v[8];
-    res->pxD = v[9];
-    res->dr = v[10];
-    res->q = v[11];
   }
   // write back (the generic consumers read these arrays; the next segment of
   // the QP reloads the column / CartPose owners' state from them, the hinge
@@ -5304,11 +5502,12 @@ __device__ void admm_segment(Ctx& c, Solver& sv, int n_iter, Norms* res)
   BSYNC();
   if (pf)
     pf[38] += clock64() - t_wb;
+  return done;
 }
 
-__device__ void admm_iterations(Ctx& c, Solver& sv, int n_iter, Norms* res)
+__device__ int admm_iterations(Ctx& c, Solver& sv, int it, int stop, int interval, Norms& nm)
 {
-  admm_segment<1, 1>(c, sv, n_iter, res);
+  return admm_segment<1, 1>(c, sv, it, stop, interval, nm);
 }
 
 #endif  // !THIP_GENERIC_ONLY
@@ -5592,18 +5791,13 @@ __device__ int qp_solve(Ctx& c, Solver& sv, bool pattern_equal)
     {
       // register-resident segment up to the next iteration that checks
       // termination or adapts rho (same iterates as admm_step)
-      int stop = os.max_iter;
-      if (ct)
-        stop = min(stop, (it + ct - 1) / ct * ct);
-      if (os.adaptive_rho && interval)
-        stop = min(stop, (it + interval - 1) / interval * interval);
-      // the segment computes the residuals of its last iterate when they are needed
-      const bool want = (ct && stop % ct == 0) || (os.adaptive_rho && interval && stop % interval == 0);
+      // (it stays resident over the stops whose decision below would be "carry
+      // on": it returns the iterations it ran, and nm of its last stop)
 #if !THIP_GENERIC_ONLY
-      admm_iterations(c, sv, stop - it + 1, want ? &nm : nullptr);
+      it += admm_iterations(c, sv, it, admm_next_stop(os, interval, it), interval, nm) - 1;
 #endif
-      have_res = want;
-      it = stop;
+      // the segment computes the residuals of its last iterate when they are needed
+      have_res = admm_stop_wants_res(os, interval, it);
     }
     else
     {
@@ -5622,13 +5816,13 @@ __device__ int qp_solve(Ctx& c, Solver& sv, bool pattern_equal)
       if (check_termination(c, nm, false))
         break;
     }
-    if (os.adaptive_rho && interval && (it % interval == 0))
+    if (admm_stop_ends_rho(os, interval, it))
     {
       if (!can_check && !have_res)
         compute_residuals(c, xc, zc, Y, nm);
       const double rn = rho_estimate(c, nm);
       const double rho = c.s->rho;
-      if (rn > rho * os.adaptive_rho_tolerance || rn < rho / os.adaptive_rho_tolerance)
+      if (rho_outside_band(os, rn, rho))
       {
         BSYNC();
         if (c.tid == 0)

@@ -33,6 +33,7 @@ TRACE_W = 16  # THIP_TRACE_W
 DEBUG_NO_SEGMENT, DEBUG_FORCE_WIDE, DEBUG_NO_BRANCH, DEBUG_STATIC_DISPATCH, DEBUG_GEN_BUILD = 1, 2, 4, 8, 16  # thip_debug_set_path flags
 DEBUG_MAIN_BUILD = 32
 DEBUG_SEG_REBUILD = 64  # the segment's packs rebuilt at every call (bitwise the same results)
+DEBUG_SEG_RETURN = 128  # the segment returns at every termination check, third infeasibility tests unused (same bits)
 
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_CONTINUOUS, JOINT_PRISMATIC = 0, 1, 2, 3
 PRIM_SPHERE, PRIM_BOX, PRIM_CAPSULE = 0, 1, 2

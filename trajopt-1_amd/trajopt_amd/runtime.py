@@ -128,7 +128,7 @@ class BatchTrustRegionSQP:
                      "gen_rhs_mr", "gen_rhs_cols", "gen_rhs_linv", "gen_dvalue_middle",
                      "n_primal_inf_full", "n_dual_inf_full", "n_factor", "gen_pre", "gen_updates",
                      "factor_blocks", "factor_twisted", "bwd_wave0_own", "gen_dvalue", "gen_middle_wait", "seg_setup", "seg_writeback",
-                     "unused39"]
+                     "n_seg_entries"]
 
     def layout(self):
         """The solve layout this context chose (thip_debug_solve_layout): branches, dofs
