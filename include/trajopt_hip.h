@@ -654,6 +654,72 @@ int thip_eval_collision(thip_eval* ev, int term, const double* x, double* record
 void thip_eval_destroy(thip_eval* ev);
 const char* thip_eval_last_error(thip_eval* ev); /* NULL: the last thip_eval_create failure */
 
+/* ---------------------------------------------------- Trajectory checking
+ * tesseract's checkTrajectory as the reference's tests pair it with every solve
+ * (trajopt/test/planning_unit.cpp:92-101, 143-148): is a joint trajectory within
+ * `margin` of the scene or of itself, and what is its clearance.  One verdict
+ * per problem of a batch, from trajectories on the host or already on the
+ * device (thip_device_x).  A thip_check holds the chain, the robot spheres, the
+ * self-collision pairs, n_prims and n_steps of a descriptor -- nothing else of
+ * it is read, so it works with or without a collision term -- and the scenes of
+ * `batch` problems.  n_steps in [1, THIP_EVAL_MAX_STEPS], n_prims in
+ * [0, THIP_EVAL_MAX_PRIMS].
+ *
+ * Units are the evaluator's: a waypoint of [first_step, last_step] for DISCRETE,
+ * else a step pair, with the LVS sub-states of the collision terms (the count
+ * of collision_terms.cpp:846-852, Eigen's LinSpaced states); the continuous
+ * kind casts every robot sphere between consecutive sub-states.  Candidates run
+ * in the flattened ContactResultMap order of thip_eval_collision (robot link,
+ * primitive, sub-state, sphere; then the self-collision pairs); a candidate is
+ * a contact when its distance < margin.  No fixed-step filter, no buffer, no
+ * per-pair margins, contact test ALL, no gradients.  The minimum is the lowest
+ * distance, ties to the earlier unit, then the earlier candidate; results are
+ * bitwise repeatable.  Distances are the closed-form primitive distances of
+ * the collision terms (THIP_PRIM_*), not Bullet's. */
+typedef struct thip_check_config {
+  int type;                   /* the coll_continuous encoding: 0 LVS_DISCRETE, 1 LVS_CONTINUOUS, 2 DISCRETE */
+  double lvs;                 /* longest_valid_segment_length (> 0 unless DISCRETE; +inf: one cast per pair) */
+  double margin;              /* contact distance, default 0 */
+  int first_step, last_step;  /* -1 = last */
+} thip_check_config;
+
+typedef struct thip_check_result {
+  int found;                  /* n_contacts > 0 */
+  int n_contacts;
+  int first_unit;             /* waypoint index of the first unit with a contact, or -1 */
+  long long n_candidates;
+  double min_distance;        /* +inf (and min_* = -1) when there is no candidate */
+  int min_t, min_link, min_other, min_sphere, min_substate; /* unit waypoint, robot link, primitive or
+                                 -1 - sphere_b, robot sphere, sub-state (0 for DISCRETE) */
+  double min_cc_time;         /* thip_eval_collision's cc_time of that candidate */
+} thip_check_result;
+
+/* sub-states (casts, for the continuous kind) whose sphere centres one chunk of
+ * the kernel holds in LDS; a step pair with more loops over chunks */
+#define THIP_CHECK_CHUNK 8
+
+typedef struct thip_check thip_check;
+void thip_default_check_config(thip_check_config* c); /* LVS_CONTINUOUS, lvs +inf, margin 0, all steps */
+int thip_sizeof_check_config(void);
+int thip_sizeof_check_result(void);
+/* Validates cfg and the descriptor fields read before any device call. */
+int thip_check_create(int device, const thip_problem_desc* desc, const thip_check_config* cfg, int batch,
+                      thip_check** out);
+/* scene [batch][n_prims][16] (NULL when n_prims = 0): host / device pointer */
+int thip_check_upload(thip_check* chk, const double* scene);
+int thip_check_upload_device(thip_check* chk, const double* d_scene);
+/* units per problem: waypoints (DISCRETE) or step pairs of [first_step, last_step] */
+int thip_check_units(const thip_check* chk);
+/* x [batch][n_steps][n_dof] -> results [batch]; unit_min [batch][n_units] each
+ * unit's smallest distance, or NULL.  Synchronous.  The _device variant reads
+ * trajectories already on the device (e.g. thip_device_x after thip_synchronize). */
+int thip_check_run(thip_check* chk, const double* x, thip_check_result* results, double* unit_min);
+int thip_check_run_device(thip_check* chk, const double* d_x, thip_check_result* results, double* unit_min);
+/* The two kernels of the last run, HIP events on the checker's stream (milliseconds; < 0: none). */
+double thip_check_last_ms(thip_check* chk);
+void thip_check_destroy(thip_check* chk);
+const char* thip_check_last_error(thip_check* chk); /* NULL: the last thip_check_create failure */
+
 /* ------------------------------------------------------------- Generic QP
  * OSQP 1.0 on an arbitrary sparse QP
  *     minimise 1/2 x'Px + q'x   subject to   l <= A x <= u

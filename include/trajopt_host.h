@@ -109,6 +109,17 @@ int thost_solve_json_stream(const char* const* json_texts, int n_batches, int ba
 int thost_solve_json(const char* json_text, const double* scene, int n_prims, int device, double* x,
                      thip_result* result, int* native, char* err, int err_len);
 
+/* trajopt::checkTrajectory (trajopt_amd/check_trajectory.hpp; thip_check_* in
+ * trajopt_hip.h) for `batch` JSON problems of one group, horizon and scene size:
+ * is each trajectory (trajectories [batch][n_steps][n_dof], joint values only)
+ * within config->margin of its scene (scenes [batch][n_prims][16] after the
+ * built-in environment's own) or of itself, and its clearance.  A problem needs
+ * no collision term.  results [batch]; `found` is the reference's
+ * checkTrajectory return value (planning_unit.cpp:92-101, 143-148). */
+int thost_check_json_batch(const char* const* json_texts, int batch, const double* scenes, int n_prims,
+                           const double* trajectories, const thip_check_config* config, int device,
+                           thip_check_result* results, char* err, int err_len);
+
 /* ---------------------------------------------------------- trajopt_sqp
  * The second SQP front end (the ifopt stack):
  * trajopt_sqp::TrustRegionSQPSolver over a trajopt_sqp::TrajOptQPProblem whose

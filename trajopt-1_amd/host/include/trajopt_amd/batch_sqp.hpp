@@ -7,6 +7,7 @@
 #include <memory>
 #include <vector>
 
+#include "trajopt_amd/check_trajectory.hpp"
 #include "trajopt_amd/problem_description.hpp"
 
 namespace trajopt
@@ -39,6 +40,11 @@ public:
   // submit() for another batch of the same structure and size on this context
   // (its device workspace is reused; collect() the previous batch first)
   void submit(std::vector<LoweredProblem> probs);
+  // checkTrajectory on the last solve's trajectories where they lie on the device
+  // (thip_device_x: no round trip), one report per problem.  Waits for the solve.
+  // A host-loop batch keeps no device trajectories: check its results with
+  // trajopt::checkTrajectory.
+  std::vector<TrajectoryCheckReport> checkResults(const CollisionCheckConfig& config = CollisionCheckConfig());
   // HIP-event duration of the last fused launch (ms).
   double lastKernelMs() const;
   // Per-QP records of the next optimize() (thip_debug_trace, THIP_TRACE_W doubles each).
@@ -76,6 +82,8 @@ private:
   int trace_cap_ = 0;
   std::vector<TrajOptProb::Ptr> generic_;  // host-loop batch
   int device_ = 0;
+  bool submitted_ = false;                 // a fused solve has been queued (thip_device_x holds its trajectories)
+  std::vector<TrajOptProb::Ptr> source_;   // fused batch built from TrajOptProbs: their environments (checkResults)
   std::vector<sco::OptResults> generic_results_;
   long long qp_launches_ = 0, qp_solves_ = 0;
   double qp_bytes_ = 0, qp_launch_s_ = 0;

@@ -386,5 +386,10 @@ private:
 };
 
 TrajOptProb::Ptr ConstructProblem(const ProblemConstructionInfo& pci);
+// The collision model of group `kin` in `env` as a descriptor holds it (robot
+// spheres, n_prims with the primitives appended to `scene`, self-collision
+// link pairs): what the first CollisionTermInfo::hatch lowers.
+void lowerCollisionModel(const KinematicGroup& kin, const Environment& env, thip_problem_desc& d,
+                         std::vector<double>& scene);
 TrajOptProb::Ptr ConstructProblem(const Json::Value& root, const Environment::ConstPtr& env);
 }  // namespace trajopt

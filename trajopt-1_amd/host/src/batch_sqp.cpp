@@ -129,6 +129,7 @@ BatchTrustRegionSQP::BatchTrustRegionSQP(const std::vector<TrajOptProb::Ptr>& pr
     return;
   }
   probs_ = lowerAll(probs);
+  source_ = probs;
   init(device);
 }
 
@@ -271,6 +272,37 @@ void BatchTrustRegionSQP::submit()
   if (d.n_jpos > 0)
     check(thip_upload_joint_targets(ctx_, jpt.data()), "thip_upload_joint_targets");
   check(thip_sqp_run(ctx_), "thip_sqp_run");
+  submitted_ = true;
+}
+
+std::vector<TrajectoryCheckReport> BatchTrustRegionSQP::checkResults(const CollisionCheckConfig& config)
+{
+  if (!generic_.empty())
+    throw std::runtime_error("BatchTrustRegionSQP::checkResults: a host-loop batch keeps no trajectories on the "
+                             "device; check its results with trajopt::checkTrajectory");
+  if (!submitted_)
+    throw std::runtime_error("BatchTrustRegionSQP::checkResults: nothing has run");
+  check(thip_synchronize(ctx_), "thip_synchronize");
+  thip_problem_desc d = probs_[0].desc;
+  std::vector<double> scenes;
+  const bool model = d.coll_enabled || d.n_coll_extra > 0;
+  for (std::size_t b = 0; b < probs_.size(); ++b)
+  {
+    if (model)
+    {
+      scenes.insert(scenes.end(), probs_[b].scene.begin(), probs_[b].scene.end());
+      continue;
+    }
+    // no collision term: the collision model of the problem's own environment
+    if (source_.size() != probs_.size())
+      throw std::runtime_error("BatchTrustRegionSQP::checkResults: the problems carry no collision model (no "
+                               "collision term, and the batch was not built from TrajOptProbs)");
+    thip_problem_desc db = probs_[b].desc;
+    lowerCollisionModel(*source_[b]->GetKin(), *source_[b]->GetEnv(), db, scenes);
+    if (b == 0)
+      d = db;
+  }
+  return checkTrajectories(d, batch(), scenes, toCheckConfig(config), device_, nullptr, thip_device_x(ctx_));
 }
 
 void BatchTrustRegionSQP::submit(std::vector<LoweredProblem> probs)
@@ -289,6 +321,7 @@ void BatchTrustRegionSQP::submit(std::vector<LoweredProblem> probs)
                                " does not share the context's structure");
   }
   probs_ = std::move(probs);
+  source_.clear();
   submit();
 }
 

@@ -6,6 +6,7 @@
 #include <exception>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "trajopt_amd/batch_sqp.hpp"
 
@@ -66,6 +67,70 @@ int thost_lower_json(const char* json_text, const double* scene, int n_prims, th
       std::copy(prob->jpos_targets.begin(), prob->jpos_targets.end(), jpos_targets);
     if (scene_out)
       std::copy(prob->scene.begin(), prob->scene.end(), scene_out);
+    setErr(err, err_len, "");
+    return 0;
+  }
+  catch (const std::exception& e)
+  {
+    setErr(err, err_len, e.what());
+    return -1;
+  }
+}
+
+int thost_check_json_batch(const char* const* json_texts, int batch, const double* scenes, int n_prims,
+                           const double* trajectories, const thip_check_config* config, int device,
+                           thip_check_result* results, char* err, int err_len)
+{
+  try
+  {
+    if (!json_texts || batch <= 0 || !trajectories || !config || !results)
+      throw std::runtime_error("thost_check_json_batch: null argument or batch <= 0");
+    // the C-ABI config back to the front door's (type: the coll_continuous encoding)
+    trajopt::CollisionCheckConfig cc;
+    if (config->type < 0 || config->type > 2)
+      throw std::runtime_error("thost_check_json_batch: bad type " + std::to_string(config->type));
+    cc.type = config->type == 2   ? trajopt::CollisionEvaluatorType::DISCRETE
+              : config->type == 0 ? trajopt::CollisionEvaluatorType::LVS_DISCRETE
+                                  : trajopt::CollisionEvaluatorType::LVS_CONTINUOUS;
+    cc.longest_valid_segment_length = config->lvs;
+    cc.contact_margin = config->margin;
+    cc.first_step = config->first_step;
+    cc.last_step = config->last_step;
+    std::vector<trajopt::TrajOptProb::Ptr> probs;
+    std::vector<trajopt::TrajArray> trajs;
+    const double* x = trajectories;
+    for (int b = 0; b < batch; ++b)
+    {
+      probs.push_back(construct(json_texts[b], scenes ? scenes + static_cast<std::size_t>(b) * n_prims * 16 : nullptr,
+                                n_prims));
+      const int N = probs.back()->GetNumSteps(), D = probs.back()->GetNumDOF();
+      trajopt::TrajArray t(static_cast<std::size_t>(N));
+      for (auto& row : t)
+      {
+        row.assign(x, x + D);
+        x += D;
+      }
+      trajs.push_back(std::move(t));
+    }
+    const auto rep = trajopt::checkTrajectory(probs, trajs, cc, device);
+    for (int b = 0; b < batch; ++b)
+    {
+      const trajopt::TrajectoryCheckReport& r = rep[static_cast<std::size_t>(b)];
+      thip_check_result o;
+      std::memset(&o, 0, sizeof(o));
+      o.found = r.found ? 1 : 0;
+      o.n_contacts = r.n_contacts;
+      o.first_unit = r.first_step;
+      o.n_candidates = r.n_candidates;
+      o.min_distance = r.min_distance;
+      o.min_t = r.min_step;
+      o.min_link = r.min_link;
+      o.min_other = r.min_other;
+      o.min_sphere = r.min_sphere;
+      o.min_substate = r.min_substate;
+      o.min_cc_time = r.min_cc_time;
+      results[b] = o;
+    }
     setErr(err, err_len, "");
     return 0;
   }

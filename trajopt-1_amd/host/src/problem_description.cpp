@@ -1017,6 +1017,66 @@ void CollisionTermInfo::fromJson(ProblemConstructionInfo& pci, const Json::Value
   ensure_only_members(params, all_fields, sizeof(all_fields) / sizeof(char*));
 }
 
+// The robot spheres on the group's links (the other robot links are outside the joint group)
+std::vector<const CollisionSphere*> robotSpheres(const KinematicGroup& kin, const Environment& env)
+{
+  std::vector<const CollisionSphere*> spheres;
+  for (const auto& cs : env.collision_spheres)
+    if (kin.linkIndex(cs.link) > 0)
+      spheres.push_back(&cs);
+  if (spheres.empty() || static_cast<int>(spheres.size()) > THIP_MAX_SPHERES)
+    unsupported("a collision model with " + std::to_string(spheres.size()) + " spheres");
+  // (a scene beyond THIP_MAX_PRIMS runs the generic path, TrajOptProb::lowerable)
+  if (static_cast<int>(env.scene.size()) > THIP_EVAL_MAX_PRIMS)
+    unsupported("a scene of more than " + std::to_string(THIP_EVAL_MAX_PRIMS) + " primitives");
+  return spheres;
+}
+
+// The collision model of a group in its environment as the descriptor holds it:
+// the robot spheres, the scene's primitives (appended to `scene`) and the
+// self-collision link pairs.  What the first collision term's hatch lowers, and
+// what checkTrajectory reads for a problem without a collision term.
+void lowerCollisionModel(const KinematicGroup& kin, const Environment& env, thip_problem_desc& d,
+                         std::vector<double>& scene)
+{
+  const std::vector<const CollisionSphere*> spheres = robotSpheres(kin, env);
+  d.n_spheres = static_cast<int>(spheres.size());
+  for (int s = 0; s < d.n_spheres; ++s)
+  {
+    const CollisionSphere& cs = *spheres[static_cast<std::size_t>(s)];
+    d.sphere_link[s] = kin.linkIndex(cs.link);
+    for (int i = 0; i < 3; ++i)
+      d.sphere_center[s][i] = cs.center[i];
+    d.sphere_radius[s] = cs.radius;
+  }
+  d.n_prims = static_cast<int>(env.scene.size());
+  for (const auto& p : env.scene)
+    scene.insert(scene.end(), p.begin(), p.end());
+  // self-collision: every pair of the group's sphere links (ascending link index) the
+  // allowed-collision matrix does not disable -- the contact manager tests all its
+  // active links against each other (collision_terms.cpp:817-898 via contactTest)
+  std::vector<std::pair<int, std::string>> slinks;
+  for (const CollisionSphere* cs : spheres)
+  {
+    const int li = kin.linkIndex(cs->link);
+    if (std::find_if(slinks.begin(), slinks.end(), [&](const auto& e) { return e.first == li; }) == slinks.end())
+      slinks.push_back({ li, cs->link });
+  }
+  std::sort(slinks.begin(), slinks.end());
+  d.n_self_pairs = 0;
+  for (std::size_t a = 0; a < slinks.size(); ++a)
+    for (std::size_t b = a + 1; b < slinks.size(); ++b)
+    {
+      if (env.isCollisionAllowed(slinks[a].second, slinks[b].second))
+        continue;
+      if (d.n_self_pairs >= THIP_MAX_SELF_PAIRS)
+        unsupported("more than " + std::to_string(THIP_MAX_SELF_PAIRS) + " self-collision link pairs");
+      d.self_pair[d.n_self_pairs][0] = slinks[a].first;
+      d.self_pair[d.n_self_pairs][1] = slinks[b].first;
+      ++d.n_self_pairs;
+    }
+}
+
 // problem_description.cpp:1735-1858: DISCRETE (single-timestep terms on the free waypoints),
 // LVS_DISCRETE, CONTINUOUS and LVS_CONTINUOUS (step-pair terms)
 void CollisionTermInfo::hatch(TrajOptProb& prob)
@@ -1040,16 +1100,7 @@ void CollisionTermInfo::hatch(TrajOptProb& prob)
     if (a && b)
       throw std::runtime_error("Currently two adjacent fixed steps are not supported in collision term.");
   }
-  // the robot spheres on the group's links (the other robot links are outside the joint group)
-  std::vector<const CollisionSphere*> spheres;
-  for (const auto& cs : env->collision_spheres)
-    if (prob.GetKin()->linkIndex(cs.link) > 0)
-      spheres.push_back(&cs);
-  if (spheres.empty() || static_cast<int>(spheres.size()) > THIP_MAX_SPHERES)
-    unsupported("a collision model with " + std::to_string(spheres.size()) + " spheres");
-  // (a scene beyond THIP_MAX_PRIMS runs the generic path, TrajOptProb::lowerable)
-  if (static_cast<int>(env->scene.size()) > THIP_EVAL_MAX_PRIMS)
-    unsupported("a scene of more than " + std::to_string(THIP_EVAL_MAX_PRIMS) + " primitives");
+  const std::vector<const CollisionSphere*> spheres = robotSpheres(*prob.GetKin(), *env);
   if (static_cast<int>(fixed_steps.size()) > THIP_MAX_STEPS)
     throw std::runtime_error("CollisionTermInfo: too many fixed steps");
   const bool is_cnt = !any(term_type & TermType::TT_COST);
@@ -1192,41 +1243,7 @@ void CollisionTermInfo::hatch(TrajOptProb& prob)
     lowerPairs();
     return;
   }
-  d.n_spheres = static_cast<int>(spheres.size());
-  for (int s = 0; s < d.n_spheres; ++s)
-  {
-    const CollisionSphere& cs = *spheres[static_cast<std::size_t>(s)];
-    d.sphere_link[s] = prob.GetKin()->linkIndex(cs.link);
-    for (int i = 0; i < 3; ++i)
-      d.sphere_center[s][i] = cs.center[i];
-    d.sphere_radius[s] = cs.radius;
-  }
-  d.n_prims = static_cast<int>(env->scene.size());
-  for (const auto& p : env->scene)
-    prob.scene.insert(prob.scene.end(), p.begin(), p.end());
-  // self-collision: every pair of the group's sphere links (ascending link index) the
-  // allowed-collision matrix does not disable -- the contact manager tests all its
-  // active links against each other (collision_terms.cpp:817-898 via contactTest)
-  std::vector<std::pair<int, std::string>> slinks;
-  for (const CollisionSphere* cs : spheres)
-  {
-    const int li = prob.GetKin()->linkIndex(cs->link);
-    if (std::find_if(slinks.begin(), slinks.end(), [&](const auto& e) { return e.first == li; }) == slinks.end())
-      slinks.push_back({ li, cs->link });
-  }
-  std::sort(slinks.begin(), slinks.end());
-  d.n_self_pairs = 0;
-  for (std::size_t a = 0; a < slinks.size(); ++a)
-    for (std::size_t b = a + 1; b < slinks.size(); ++b)
-    {
-      if (env->isCollisionAllowed(slinks[a].second, slinks[b].second))
-        continue;
-      if (d.n_self_pairs >= THIP_MAX_SELF_PAIRS)
-        unsupported("more than " + std::to_string(THIP_MAX_SELF_PAIRS) + " self-collision link pairs");
-      d.self_pair[d.n_self_pairs][0] = slinks[a].first;
-      d.self_pair[d.n_self_pairs][1] = slinks[b].first;
-      ++d.n_self_pairs;
-    }
+  lowerCollisionModel(*prob.GetKin(), *env, d, prob.scene);
   lowerPairs();
 }
 

@@ -1,8 +1,11 @@
 // trajopt_batch: solve JSON problems (the reference's TrajOptRequest format)
 // as one batch on one MI355X through the C++ front door.
-//   trajopt_batch [--device D] [--repeat R] problem.json [problem.json ...]
+//   trajopt_batch [--device D] [--repeat R] [--check] problem.json [problem.json ...]
 // Every file is one problem (all must share one structure); --repeat R
-// replicates the list R times.  Prints one line per problem.
+// replicates the list R times.  Prints one line per problem.  --check: after
+// the solve, each problem's checkTrajectory verdict (a CONTINUOUS check with
+// margin 0, as planning_unit.cpp runs it) and clearance, from the trajectories
+// on the device.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +18,7 @@
 int main(int argc, char** argv)
 {
   int device = 0, repeat = 1;
+  bool do_check = false;
   std::vector<std::string> files;
   for (int i = 1; i < argc; ++i)
   {
@@ -22,12 +26,14 @@ int main(int argc, char** argv)
       device = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--repeat") && i + 1 < argc)
       repeat = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--check"))
+      do_check = true;
     else
       files.emplace_back(argv[i]);
   }
   if (files.empty() || repeat < 1)
   {
-    std::fprintf(stderr, "usage: %s [--device D] [--repeat R] problem.json [...]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [--device D] [--repeat R] [--check] problem.json [...]\n", argv[0]);
     return 2;
   }
   try
@@ -44,6 +50,30 @@ int main(int argc, char** argv)
                   sco::toString(res[b].status).c_str(), res[b].n_sqp_iters, res[b].n_qp_solves, res[b].total_cost,
                   res[b].max_cnt_viol);
     std::printf("kernel %.3f ms for %zu problems\n", opt.lastKernelMs(), res.size());
+    if (do_check)
+    {
+      // a host-loop batch keeps its trajectories on the host
+      std::vector<trajopt::TrajectoryCheckReport> rep;
+      if (opt.hostLoops())
+      {
+        std::vector<trajopt::TrajArray> trajs;
+        for (std::size_t b = 0; b < res.size(); ++b)
+        {
+          const std::size_t N = static_cast<std::size_t>(probs[b]->GetNumSteps()), W = res[b].x.size() / N;
+          trajopt::TrajArray t;
+          for (std::size_t i = 0; i < N; ++i)
+            t.emplace_back(res[b].x.begin() + static_cast<long>(i * W), res[b].x.begin() + static_cast<long>((i + 1) * W));
+          trajs.push_back(std::move(t));
+        }
+        rep = trajopt::checkTrajectory(probs, trajs, trajopt::CollisionCheckConfig(), device);
+      }
+      else
+        rep = opt.checkResults();
+      for (std::size_t b = 0; b < rep.size(); ++b)
+        std::printf("problem %zu: check %s contacts %d clearance %.9g at step %d link %d other %d\n", b,
+                    rep[b].found ? "IN_COLLISION" : "collision_free", rep[b].n_contacts, rep[b].min_distance,
+                    rep[b].min_step, rep[b].min_link, rep[b].min_other);
+    }
   }
   catch (const std::exception& e)
   {

@@ -30,6 +30,8 @@ MAX_COLL_PAIRS = 64
 EVAL_MAX_STEPS = 4096  # THIP_EVAL_MAX_STEPS: the generic path's horizon
 EVAL_MAX_PRIMS = 1024  # THIP_EVAL_MAX_PRIMS
 TRACE_W = 16  # THIP_TRACE_W
+CHECK_CHUNK = 8  # THIP_CHECK_CHUNK: sub-states per chunk of the trajectory checker's kernel
+CHECK_LVS_DISCRETE, CHECK_LVS_CONTINUOUS, CHECK_DISCRETE = 0, 1, 2  # thip_check_config.type (the coll_continuous encoding)
 DEBUG_NO_SEGMENT, DEBUG_FORCE_WIDE, DEBUG_NO_BRANCH, DEBUG_STATIC_DISPATCH, DEBUG_GEN_BUILD = 1, 2, 4, 8, 16  # thip_debug_set_path flags
 DEBUG_MAIN_BUILD = 32
 DEBUG_SEG_REBUILD = 64  # the segment's packs rebuilt at every call (bitwise the same results)
@@ -259,6 +261,39 @@ class Result(C.Structure):
     ]
 
 
+class CheckConfig(C.Structure):
+    """thip_check_config: what a trajectory check tests."""
+    _fields_ = [
+        ("type", C.c_int),
+        ("lvs", C.c_double),
+        ("margin", C.c_double),
+        ("first_step", C.c_int),
+        ("last_step", C.c_int),
+    ]
+
+
+class CheckResult(C.Structure):
+    """thip_check_result: one problem's verdict and clearance."""
+    _fields_ = [
+        ("found", C.c_int),
+        ("n_contacts", C.c_int),
+        ("first_unit", C.c_int),
+        ("n_candidates", C.c_longlong),
+        ("min_distance", C.c_double),
+        ("min_t", C.c_int),
+        ("min_link", C.c_int),
+        ("min_other", C.c_int),
+        ("min_sphere", C.c_int),
+        ("min_substate", C.c_int),
+        ("min_cc_time", C.c_double),
+    ]
+
+
+def default_check_config() -> CheckConfig:
+    """thip_default_check_config: one cast per step pair (CONTINUOUS), margin 0, every step."""
+    return CheckConfig(CHECK_LVS_CONTINUOUS, float("inf"), 0.0, 0, -1)
+
+
 def default_sqp_params() -> SqpParams:
     """sco::BasicTrustRegionSQPParameters defaults (optimizers.hpp:92-135)."""
     p = SqpParams()
@@ -377,6 +412,30 @@ def _declare(lib):
     lib.thip_eval_destroy.restype = None
     lib.thip_eval_last_error.argtypes = [vp]
     lib.thip_eval_last_error.restype = C.c_char_p
+    lib.thip_default_check_config.argtypes = [P(CheckConfig)]
+    lib.thip_default_check_config.restype = None
+    lib.thip_sizeof_check_config.argtypes = []
+    lib.thip_sizeof_check_config.restype = C.c_int
+    lib.thip_sizeof_check_result.argtypes = []
+    lib.thip_sizeof_check_result.restype = C.c_int
+    lib.thip_check_create.argtypes = [C.c_int, P(ProblemDesc), P(CheckConfig), C.c_int, P(vp)]
+    lib.thip_check_create.restype = C.c_int
+    lib.thip_check_upload.argtypes = [vp, dp]
+    lib.thip_check_upload.restype = C.c_int
+    lib.thip_check_upload_device.argtypes = [vp, vp]
+    lib.thip_check_upload_device.restype = C.c_int
+    lib.thip_check_units.argtypes = [vp]
+    lib.thip_check_units.restype = C.c_int
+    lib.thip_check_run.argtypes = [vp, dp, P(CheckResult), dp]
+    lib.thip_check_run.restype = C.c_int
+    lib.thip_check_run_device.argtypes = [vp, vp, P(CheckResult), dp]
+    lib.thip_check_run_device.restype = C.c_int
+    lib.thip_check_last_ms.argtypes = [vp]
+    lib.thip_check_last_ms.restype = C.c_double
+    lib.thip_check_destroy.argtypes = [vp]
+    lib.thip_check_destroy.restype = None
+    lib.thip_check_last_error.argtypes = [vp]
+    lib.thip_check_last_error.restype = C.c_char_p
     lib.thip_sizeof_desc.argtypes = []
     lib.thip_sizeof_desc.restype = C.c_int
     lib.thip_sizeof_result.argtypes = []
@@ -404,6 +463,9 @@ def load_hip():
         _hip = _declare(C.CDLL(str(HIP_LIB)))
         if _hip.thip_sizeof_desc() != C.sizeof(ProblemDesc) or _hip.thip_sizeof_result() != C.sizeof(Result):
             raise RuntimeError("thip_problem_desc / thip_result layout mismatch between Python and the HIP library")
+        if (_hip.thip_sizeof_check_config() != C.sizeof(CheckConfig)
+                or _hip.thip_sizeof_check_result() != C.sizeof(CheckResult)):
+            raise RuntimeError("thip_check_config / thip_check_result layout mismatch between Python and the HIP library")
     return _hip
 
 

@@ -63,6 +63,10 @@ def load_host():
         L.thost_batch_qp_shape.restype = C.c_int
         L.thost_batch_destroy.argtypes = [C.c_void_p]
         L.thost_batch_destroy.restype = None
+        L.thost_check_json_batch.argtypes = [C.POINTER(C.c_char_p), C.c_int, dp, C.c_int, dp,
+                                             C.POINTER(abi.CheckConfig), C.c_int, C.POINTER(abi.CheckResult),
+                                             C.c_char_p, C.c_int]
+        L.thost_check_json_batch.restype = C.c_int
         L.thost_solve_json.argtypes = [C.c_char_p, dp, C.c_int, C.c_int, dp, C.POINTER(abi.Result),
                                        C.POINTER(C.c_int), C.c_char_p, C.c_int]
         L.thost_solve_json.restype = C.c_int
@@ -120,6 +124,28 @@ def solve_json_batch(texts, scenes=None, device=0, devices=None):
     if rc != 0:
         raise HostError(err.value.decode())
     return x, list(res)
+
+
+def check_json_batch(texts, scenes, trajectories, config=None, device=0):
+    """trajopt::checkTrajectory for JSON problems (thost_check_json_batch): is each
+    trajectory (trajectories [B, N, D], joint values) within config.margin of its
+    scene or of itself -> list of abi.CheckResult (`found`: the reference's
+    checkTrajectory return value).  config: abi.CheckConfig (default: CONTINUOUS,
+    margin 0).  The problems need no collision term."""
+    L = load_host()
+    B = len(texts)
+    sc = None if scenes is None else np.ascontiguousarray(scenes, dtype=np.float64)
+    n_prims = 0 if sc is None else sc.shape[1]
+    x = np.ascontiguousarray(trajectories, dtype=np.float64)
+    if x.ndim != 3 or x.shape[0] != B:
+        raise HostError(f"check_json_batch: trajectories of shape {x.shape} for {B} problems")
+    cfg = abi.default_check_config() if config is None else config
+    arr = (C.c_char_p * B)(*[t.encode() for t in texts])
+    res = (abi.CheckResult * B)()
+    err = C.create_string_buffer(4096)
+    if L.thost_check_json_batch(arr, B, _dp(sc), n_prims, _dp(x), C.byref(cfg), device, res, err, 4096) != 0:
+        raise HostError(err.value.decode())
+    return list(res)
 
 
 def last_batch_qp_stats():

@@ -28,6 +28,7 @@ class BatchTrustRegionSQP:
         self.wl = workload
         self.batch = workload.batch
         self.ctx = C.c_void_p()
+        self._device = device
         rc = self.lib.thip_create(device, C.byref(workload.desc), self.batch, C.byref(self.ctx))
         if rc != 0:
             raise HipError(f"thip_create: {self.lib.thip_last_error(None).decode()}")
@@ -110,6 +111,17 @@ class BatchTrustRegionSQP:
                 raise HipError(f"problem {b}: contact overflow")
             out.append(rec[b, : min(cnt[b], cap)])
         return out
+
+    def check(self, config=None, unit_min=False):
+        """checkTrajectory on the last solve's trajectories where they lie on the
+        device (thip_device_x): list of abi.CheckResult, one per problem (and the
+        per-unit clearance [B, n_units] with unit_min)."""
+        self.sync()
+        chk = TrajectoryChecker(self.wl.desc, self.batch, self.wl.scene, config, device=self._device)
+        try:
+            return chk.run_device(self.lib.thip_device_x(self.ctx), unit_min=unit_min)
+        finally:
+            chk.close()
 
     def enable_trace(self, capacity=512):
         self._trace_cap = capacity
@@ -206,6 +218,70 @@ class TermEvaluator:
         if self.ev:
             self.lib.thip_eval_destroy(self.ev)
             self.ev = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TrajectoryChecker:
+    """thip_check_*: tesseract's checkTrajectory for a batch -- per problem, is the
+    joint trajectory within `margin` of its scene or of itself, how many such
+    contacts, and the smallest signed distance with where it occurs.  Reads the
+    chain, robot spheres, self-collision pairs, n_prims and n_steps of `desc`
+    (a collision term is not needed); scene [B, n_prims, 16]."""
+
+    def __init__(self, desc, batch, scene, config=None, device: int = 0):
+        self.lib = abi.load_hip()
+        self.batch = batch
+        self.n_steps, self.n_dof = desc.n_steps, desc.chain.n_dof
+        self.config = abi.default_check_config() if config is None else config
+        self.chk = C.c_void_p()
+        rc = self.lib.thip_check_create(device, C.byref(desc), C.byref(self.config), batch, C.byref(self.chk))
+        if rc != 0:
+            raise HipError(f"thip_check_create: {self.lib.thip_check_last_error(None).decode()}")
+        self.n_units = self.lib.thip_check_units(self.chk)
+        self._scene = np.ascontiguousarray(scene, dtype=np.float64) if desc.n_prims > 0 else None
+        if self._scene is not None and self._scene.size != batch * desc.n_prims * 16:
+            self.close()
+            raise HipError(f"TrajectoryChecker: scene has {self._scene.size} values, not [batch][n_prims][16]")
+        self._check(self.lib.thip_check_upload(self.chk, None if self._scene is None else _dp(self._scene)),
+                    "thip_check_upload")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise HipError(f"{what}: {self.lib.thip_check_last_error(self.chk).decode()}")
+
+    def _out(self, unit_min):
+        res = (abi.CheckResult * self.batch)()
+        um = np.zeros((self.batch, self.n_units)) if unit_min else None
+        return res, um
+
+    def run(self, x, unit_min=False):
+        """x [B, N, D] (host) -> list of abi.CheckResult (, unit_min [B, n_units])."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != self.batch * self.n_steps * self.n_dof:
+            raise HipError(f"TrajectoryChecker.run: x has {x.size} values, not [batch][n_steps][n_dof]")
+        res, um = self._out(unit_min)
+        self._check(self.lib.thip_check_run(self.chk, _dp(x), res, None if um is None else _dp(um)), "thip_check_run")
+        return (list(res), um) if unit_min else list(res)
+
+    def run_device(self, d_x, unit_min=False):
+        """As run() on trajectories already on the device (an address, e.g. thip_device_x)."""
+        res, um = self._out(unit_min)
+        self._check(self.lib.thip_check_run_device(self.chk, C.c_void_p(d_x), res, None if um is None else _dp(um)),
+                    "thip_check_run_device")
+        return (list(res), um) if unit_min else list(res)
+
+    def kernel_ms(self) -> float:
+        return float(self.lib.thip_check_last_ms(self.chk))
+
+    def close(self):
+        if self.chk:
+            self.lib.thip_check_destroy(self.chk)
+            self.chk = C.c_void_p()
 
     def __del__(self):
         try:
