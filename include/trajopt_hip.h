@@ -720,6 +720,72 @@ double thip_check_last_ms(thip_check* chk);
 void thip_check_destroy(thip_check* chk);
 const char* thip_check_last_error(thip_check* chk); /* NULL: the last thip_check_create failure */
 
+/* ------------------------------------------------------------ Term values
+ * OptResults::cost_vals / cnt_viols (trajopt_sco/src/optimizers.cpp:176-192,
+ * 908-909, 976) for a batch: the exact value of every cost and the violation of
+ * every constraint of every problem at trajectories x, on the host or already
+ * on the device (thip_device_x).  The fused kernel keeps these per-slot values
+ * in its workspace and returns only their sum and maximum (thip_result); this
+ * evaluator restates its evaluate() outside it, for any x.  Domain: the
+ * descriptors thip_create accepts; anything else is refused before any device
+ * call (several collision terms, time terms, non-fused JointAcc / JointJerk
+ * terms and horizons beyond THIP_MAX_STEPS are answered by Cost::value /
+ * Constraint::violation on the host loop).  With contact test FIRST / CLOSEST
+ * the collision slots are sums over thip_eval_collision's records (the
+ * selection is made there), which pass through the host.
+ *
+ * Slots are the fused kernel's: cost slots [JointVel | CartPose costs | JointPos
+ * costs | further JointVel costs | JointAcc | collision units], constraint slots
+ * [CartPose constraints | JointPos constraints | further JointVel constraints |
+ * collision units].  A collision unit's value is the sum over its contacts of
+ * coeff * max(margin - distance, 0) (no buffer in the value), contacts chosen
+ * as the collision terms choose them (margin + buffer, per-pair tables, the
+ * fixed-end filter).  Results are bitwise repeatable and do not depend on a
+ * problem's position in the batch. */
+#define THIP_TERM_JOINT_VEL 0 /* the jv_* term (cost slot 0) */
+#define THIP_TERM_JVX 1       /* jvx term `index` */
+#define THIP_TERM_JPOS 2      /* jpos term `index` */
+#define THIP_TERM_JDT 3       /* jdt term `index` (JointAccEqCost) */
+#define THIP_TERM_CART 4      /* cart term `index` */
+#define THIP_TERM_COLL 5      /* collision unit `index` (waypoint `unit`) */
+typedef struct thip_term_slot {
+  int kind;   /* THIP_TERM_* */
+  int index;  /* within the kind, descriptor order */
+  int unit;   /* first waypoint of a collision unit, else -1 */
+  int is_cnt; /* 0: a cost slot, 1: a constraint slot */
+} thip_term_slot;
+
+typedef struct thip_terms thip_terms;
+int thip_sizeof_term_slot(void);
+/* Validates the descriptor before any device call. */
+int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip_terms** out);
+/* The slot counts and table of a descriptor without an evaluator or a device:
+ * up to `cap` entries to out (NULL with cap 0), the same validation. */
+int thip_terms_slot_table(const thip_problem_desc* desc, thip_term_slot* out, int cap, int* n_costs, int* n_cnts);
+int thip_terms_counts(const thip_terms* t, int* n_costs, int* n_cnts);
+/* out [n_costs + n_cnts]: the cost slots in order, then the constraint slots */
+int thip_terms_slots(const thip_terms* t, thip_term_slot* out);
+/* cart_targets [batch][n_cart][12], scene [batch][n_prims][16] (NULL when empty):
+ * host / device pointers, as thip_upload / thip_upload_device */
+int thip_terms_upload(thip_terms* t, const double* cart_targets, const double* scene);
+int thip_terms_upload_device(thip_terms* t, const double* d_cart_targets, const double* d_scene);
+/* per-problem JointPos targets [batch][n_jpos][n_dof]; without this call every
+ * problem uses desc->jpos_targets (thip_upload_joint_targets) */
+int thip_terms_upload_joint_targets(thip_terms* t, const double* jpos_targets);
+int thip_terms_upload_joint_targets_device(thip_terms* t, const double* d_jpos_targets);
+/* x [batch][n_steps][n_dof] -> costs [batch][n_costs], viols [batch][n_cnts]
+ * (host arrays; NULL allowed for an empty one).  Synchronous.  The _device
+ * variant reads trajectories on the device (e.g. thip_device_x after
+ * thip_synchronize). */
+int thip_terms_run(thip_terms* t, const double* x, double* costs, double* viols);
+int thip_terms_run_device(thip_terms* t, const double* d_x, double* costs, double* viols);
+/* The last run between HIP events on the evaluator's stream (milliseconds; < 0:
+ * none): its kernels, and with contact test FIRST / CLOSEST also the records'
+ * trip through the host that lies between them. */
+double thip_terms_last_ms(thip_terms* t);
+void thip_terms_destroy(thip_terms* t);
+const char* thip_terms_last_error(thip_terms* t); /* NULL: the last thip_terms_create failure */
+
 /* ------------------------------------------------------------- Generic QP
  * OSQP 1.0 on an arbitrary sparse QP
  *     minimise 1/2 x'Px + q'x   subject to   l <= A x <= u

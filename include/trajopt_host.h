@@ -120,6 +120,41 @@ int thost_check_json_batch(const char* const* json_texts, int batch, const doubl
                            const double* trajectories, const thip_check_config* config, int device,
                            thip_check_result* results, char* err, int err_len);
 
+/* trajopt::TermEvaluator (trajopt_amd/term_evaluator.hpp; thip_terms_* in
+ * trajopt_hip.h) for `batch` lowerable JSON problems of one structure: the value
+ * of every cost and the violation of every constraint of each problem at its
+ * trajectory (trajectories [batch][n_steps][n_dof]), in prob->getCosts() /
+ * getConstraints() order (equality constraints first).
+ *   route THOST_EVAL_DEVICE   the batched term-value kernels (one evaluator)
+ *         THOST_EVAL_OBJECTS  the host term objects, Cost::value /
+ *                             Constraint::violation per problem (the device
+ *                             evaluators of the host loop)
+ *         THOST_EVAL_NAMES    counts, names and the slot map only: no device call
+ * n_costs / n_cnts: the counts.  cost_vals [batch][n_costs], cnt_viols
+ * [batch][n_cnts] (may be NULL with THOST_EVAL_NAMES).  names: problem 0's cost
+ * names, then its constraint names, each followed by '\n' (may be NULL).
+ * slot_map [n_costs + n_cnts] (may be NULL): the getCosts() position of every
+ * kernel cost slot, then the getConstraints() position of every constraint slot. */
+#define THOST_EVAL_DEVICE 0
+#define THOST_EVAL_OBJECTS 1
+#define THOST_EVAL_NAMES 2
+int thost_eval_json_batch(const char* const* json_texts, int batch, const double* scenes, int n_prims,
+                          const double* trajectories, int route, int device, int* n_costs, int* n_cnts,
+                          double* cost_vals, double* cnt_viols, char* names, int names_len, int* slot_map, char* err,
+                          int err_len);
+
+/* Solve `batch` JSON problems of one structure and return OptResults::cost_vals /
+ * cnt_viols with the usual results: through trajopt::BatchTrustRegionSQP
+ * (drop_in = 0) or problem by problem through the trajopt::BasicTrustRegionSQP
+ * drop-in (drop_in = 1: initialize, optimize, results()).  sizes[0] / sizes[1]:
+ * the lengths of problem 0's cost_vals / cnt_viols; cost_vals
+ * [batch][cap_costs] and cnt_viols [batch][cap_cnts] take each problem's
+ * vectors (an error when one is longer than its cap). */
+int thost_solve_json_batch_terms(const char* const* json_texts, int batch, const double* scenes, int n_prims,
+                                 int device, int drop_in, double* x, thip_result* results, int* sizes,
+                                 double* cost_vals, int cap_costs, double* cnt_viols, int cap_cnts, char* err,
+                                 int err_len);
+
 /* ---------------------------------------------------------- trajopt_sqp
  * The second SQP front end (the ifopt stack):
  * trajopt_sqp::TrustRegionSQPSolver over a trajopt_sqp::TrajOptQPProblem whose

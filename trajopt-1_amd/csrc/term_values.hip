@@ -1,0 +1,1237 @@
+// Batched per-term values (include/trajopt_hip.h thip_terms_*): the exact value
+// of every cost and the violation of every constraint of every problem of a
+// batch at trajectories x [batch][n_steps][n_dof] -- OptResults::cost_vals /
+// cnt_viols (trajopt_sco/src/optimizers.cpp:176-192, 908-909) for the problem
+// structures the fused kernel lowers, at any x, outside the fused kernel.
+//
+//   term_values_kernel  one 256-thread workgroup per problem: the JointVel,
+//                       JointAcc, CartPose / DynamicCartPose and JointPos slots,
+//                       the expressions of sqp_kernel.hip's evaluate(),
+//                       jpos_values(), sh_values() and jacc_value().
+//   coll_values_kernel  one 256-thread workgroup per (collision unit, problem),
+//                       traj_check_kernel's shape: one chain_fk per (sub-state,
+//                       sphere-carrying link) into LDS, kChunk sub-states at a
+//                       time, threads striding over the chunk's candidates.  A
+//                       candidate within margin + buffer of its pair that passes
+//                       the fixed-end filter of removeInvalidContactResults (as
+//                       coll_scan_pairs / coll_eval_kernel apply it) adds
+//                       coeff * max(margin - d, 0) to the unit's slot.
+// Sums are reduced by shuffles inside a wave and through LDS in wave order: no
+// floating-point atomics, no hand-off between workgroups, so the values are
+// bitwise repeatable and do not depend on a problem's position in the batch.
+// fp64; kinematics and distances are kin_device.hpp's / collision_device.hpp's.
+//
+// Slots are numbered as thip_create numbers Layout::n_costs / n_cnts,
+// jacc_slot, coll_cost0 and Tables::term_slot / jpos_slot / jvx_slot /
+// coll_slot (number_slots below restates that numbering; tests pin it against
+// the solver's A_COST / A_VIOL).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "collision_device.hpp"
+#include "kin_device.hpp"
+#include "layout.hpp"
+#include "pair_data.hpp"
+#include "self_pairs.hpp"
+
+namespace thip
+{
+namespace tv
+{
+constexpr int kTvBlock = 256;
+constexpr int kTvWaves = kTvBlock / 64;
+constexpr int kChunk = THIP_CHECK_CHUNK;
+
+// what the kernels read besides the descriptor: the slot tables
+struct Slots
+{
+  int N, D, n_costs, n_cnts;
+  int jv_eq;  // JointVelEqCost in cost slot 0
+  int jv_ineq, jv_first, jv_last;
+  int n_jacc, jacc_slot[THIP_MAX_JDT];
+  int n_cart, term_nrow[THIP_MAX_CART], term_slot[THIP_MAX_CART], row_comp[THIP_MAX_CART][6];
+  double row_w[THIP_MAX_CART][6];
+  int n_jpos, jpos_first[THIP_MAX_JPOS], jpos_last[THIP_MAX_JPOS], jpos_slot[THIP_MAX_JPOS], jpos_ineq[THIP_MAX_JPOS];
+  int n_jvx, jvx_first[THIP_MAX_JVX], jvx_last[THIP_MAX_JVX], jvx_slot[THIP_MAX_JVX];
+  // collision units (step pairs, or free waypoints for DISCRETE) and their slots
+  int coll, coll_single, coll_cnt, coll_cost0, n_units;
+  int unit_t[THIP_MAX_STEPS], unit_slot[THIP_MAX_STEPS], coll_fixed[THIP_MAX_STEPS];
+};
+
+// the robot spheres grouped by link, ascending, and the self-collision sphere pairs
+struct Model
+{
+  int n_sph, n_groups, n_prims;
+  int grp_link[THIP_MAX_SPHERES];
+  int grp_s0[THIP_MAX_SPHERES];
+  int grp_ns[THIP_MAX_SPHERES];
+  int sph_order[THIP_MAX_SPHERES];
+  double center[THIP_MAX_SPHERES][3];
+  double radius[THIP_MAX_SPHERES];
+  int n_self_sph;
+  int self_sa[THIP_MAX_SELF_SPHERE_PAIRS];
+  int self_sb[THIP_MAX_SELF_SPHERE_PAIRS];
+  int continuous;
+  double lvs, margin, coeff, buffer;
+};
+
+__device__ __forceinline__ void stage_chain_tv(thip_chain& dst_chain, const thip_chain* chain)
+{
+  const int* src = reinterpret_cast<const int*>(chain);
+  int* dst = reinterpret_cast<int*>(&dst_chain);
+  for (int w = threadIdx.x; w < static_cast<int>(sizeof(thip_chain) / 4); w += kTvBlock)
+    dst[w] = src[w];
+}
+
+// the workgroup's sum, the same bits on every thread: lanes by xor shuffles, then
+// the waves' sums in wave order
+__device__ __forceinline__ double block_sum_tv(double v, double* s_w)
+{
+  for (int off = 32; off > 0; off >>= 1)
+    v += __shfl_xor(v, off);
+  __syncthreads();  // the previous sum's reads of s_w
+  if ((threadIdx.x & 63) == 0)
+    s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = s_w[0];
+  for (int w = 1; w < kTvWaves; ++w)
+    s += s_w[w];
+  return s;
+}
+
+__global__ __launch_bounds__(kTvBlock) void term_values_kernel(const thip_problem_desc* desc, const Slots* slots,
+                                                              int batch, const double* xin, const double* tgt_all,
+                                                              const double* jpt_all, double* costs_all,
+                                                              double* viols_all)
+{
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (b >= batch)
+    return;
+  __shared__ thip_chain s_chain;
+  __shared__ double s_w[kTvWaves];
+  stage_chain_tv(s_chain, &desc->chain);
+  __syncthreads();
+  const thip_chain& ch = s_chain;
+  const thip_problem_desc& d = *desc;
+  const Slots& S = *slots;
+  const int D = S.D;
+  const double* x = xin + static_cast<long long>(b) * S.N * D;
+  const double* tgt = tgt_all + static_cast<long long>(b) * (S.n_cart > 0 ? S.n_cart : 1) * 12;
+  const double* jpt = jpt_all + static_cast<long long>(b) * (S.n_jpos > 0 ? S.n_jpos : 1) * D;
+  double* costs = costs_all + static_cast<long long>(b) * (S.n_costs > 0 ? S.n_costs : 1);
+  double* viols = viols_all + static_cast<long long>(b) * (S.n_cnts > 0 ? S.n_cnts : 1);
+
+  // JointVelEqCost::value: sum_{t,j} c_j (x_{t+1,j} - x_{t,j} - targ_j)^2
+  if (S.jv_eq)
+  {
+    const int nv = (S.jv_last - S.jv_first) * D;
+    double jv = 0;
+    for (int i = tid; i < nv; i += kTvBlock)
+    {
+      const int t = S.jv_first + i / D, j = i % D;
+      if (t < 0 || t + 1 >= S.N)
+        continue;
+      const double dd = (x[(t + 1) * D + j] - x[t * D + j]) - d.jv_targets[j];
+      jv += (dd * dd) * d.jv_coeffs[j];
+    }
+    jv = block_sum_tv(jv, s_w);
+    if (tid == 0)
+      costs[0] = jv;
+  }
+  // JointAccEqCost::value: the repeated difference as diffAxis0 forms it
+  for (int k = 0; k < S.n_jacc; ++k)
+  {
+    const int f = d.jdt_first_step[k], n = (d.jdt_last_step[k] - 2 - f + 1) * D;
+    double v = 0;
+    for (int e = tid; e < n; e += kTvBlock)
+    {
+      const int i = f + e / D, j = e % D;
+      if (i < 0 || i + 2 >= S.N)
+        continue;
+      const double x0 = x[i * D + j], x1 = x[(i + 1) * D + j], x2 = x[(i + 2) * D + j];
+      const double dd = ((x2 - x1) - (x1 - x0)) - d.jdt_targets[k][j];
+      v += (dd * dd) * d.jdt_coeffs[k][j];
+    }
+    v = block_sum_tv(v, s_w);
+    if (tid == 0)
+      costs[S.jacc_slot[k]] = v;
+  }
+  // CartPose / DynamicCartPose: one term per thread
+  for (int k = tid; k < S.n_cart; k += kTvBlock)
+  {
+    const int t = d.cart_step[k];
+    Pose P, So, Ss, Tb, To, Tt, Ti;
+    chain_fk(ch, x + t * D, d.cart_source_link[k], P);
+    pose_load(So, d.cart_source_offset[k]);
+    pose_mul(P, So, Ss);
+    pose_load(To, tgt + 12 * k);
+    if (d.cart_target_link[k] > 0)
+      chain_fk(ch, x + t * D, d.cart_target_link[k], Tb);
+    else
+      pose_load(Tb, ch.base_pose);
+    pose_mul(Tb, To, Tt);
+    pose_inv(Tt, Ti);
+    double err[6];
+    transform_error(Ti, Ss, err);
+    if (d.cart_has_tol[k])
+      apply_tolerances(err, d.cart_lower_tol[k], d.cart_upper_tol[k]);
+    const int nr = S.term_nrow[k];
+    double v = 0;
+    if (d.cart_is_cnt[k])
+    {
+      for (int rr = 0; rr < nr; ++rr)
+        v += fabs(err[S.row_comp[k][rr]] * S.row_w[k][rr]);
+      viols[S.term_slot[k]] = v;
+    }
+    else
+    {
+      for (int rr = 0; rr < nr; ++rr)
+        v += fabs(err[S.row_comp[k][rr]]) * S.row_w[k][rr];
+      costs[S.term_slot[k]] = v;
+    }
+  }
+  // JointPosEqCost::value / JointPosEqConstraint violation (sum |c_j (x - targ)^2|)
+  for (int k = 0; k < S.n_jpos; ++k)
+  {
+    const int f = S.jpos_first[k], n = (S.jpos_last[k] - f + 1) * D;
+    const bool cnt = d.jpos_is_cnt[k] != 0;
+    double s1 = 0, s2 = 0;
+    if (!S.jpos_ineq[k])
+    {
+      for (int i = tid; i < n; i += kTvBlock)
+      {
+        const int t = f + i / D, j = i % D;
+        const double dd = x[t * D + j] - jpt[k * D + j];
+        const double e = (dd * dd) * d.jpos_coeffs[k][j];
+        s1 += cnt ? fabs(e) : e;
+      }
+      s1 = block_sum_tv(s1, s_w);
+    }
+    else
+    {
+      // tolerance forms: JointPosIneqCost::value / JointPosIneqConstraint violation
+      for (int i = tid; i < n; i += kTvBlock)
+      {
+        const int t = f + i / D, j = i % D;
+        const double cf = d.jpos_coeffs[k][j];
+        const double d0 = x[t * D + j] - jpt[k * D + j];
+        s1 += fmax((d0 - d.jpos_upper_tols[k][j]) * cf, 0.0);
+        s2 += fmax(((d0 * -1) + d.jpos_lower_tols[k][j]) * cf, 0.0);
+      }
+      s1 = block_sum_tv(s1, s_w);
+      s2 = block_sum_tv(s2, s_w);
+      s1 = s1 + s2;
+    }
+    if (tid == 0)
+      (cnt ? viols : costs)[S.jpos_slot[k]] = s1;
+  }
+  // JointVelIneqCost::value (cost slot 0) and the further JointVel tolerance terms
+  for (int xo = -1; xo < S.n_jvx; ++xo)
+  {
+    if (xo < 0 && !S.jv_ineq)
+      continue;
+    const int f = (xo < 0) ? S.jv_first : S.jvx_first[xo];
+    const int nv = (((xo < 0) ? S.jv_last : S.jvx_last[xo]) - f) * D;
+    const double* cfs = (xo < 0) ? d.jv_coeffs : d.jvx_coeffs[xo];
+    const double* tg = (xo < 0) ? d.jv_targets : d.jvx_targets[xo];
+    const double* up = (xo < 0) ? d.jv_upper_tols : d.jvx_upper_tols[xo];
+    const double* lo = (xo < 0) ? d.jv_lower_tols : d.jvx_lower_tols[xo];
+    double s1 = 0, s2 = 0;
+    for (int i = tid; i < nv; i += kTvBlock)
+    {
+      const int t = f + i / D, j = i % D;
+      if (t < 0 || t + 1 >= S.N)
+        continue;
+      const double cf = cfs[j];
+      const double d0 = (x[(t + 1) * D + j] - x[t * D + j]) - tg[j];
+      s1 += fmax((d0 - up[j]) * cf, 0.0);
+      s2 += fmax(((d0 * -1) + lo[j]) * cf, 0.0);
+    }
+    s1 = block_sum_tv(s1, s_w);
+    s2 = block_sum_tv(s2, s_w);
+    if (tid == 0)
+    {
+      if (xo < 0)
+        costs[0] = s1 + s2;
+      else
+        (d.jvx_is_cnt[xo] ? viols : costs)[S.jvx_slot[xo]] = s1 + s2;
+    }
+  }
+}
+
+__device__ __forceinline__ void sphere_world_tv(const Pose& T, const double* cl, double* c)
+{
+  for (int r = 0; r < 3; ++r)
+    c[r] = T.r[r * 3 + 0] * cl[0] + T.r[r * 3 + 1] * cl[1] + T.r[r * 3 + 2] * cl[2] + T.t[r];
+}
+
+__global__ __launch_bounds__(kTvBlock) void coll_values_kernel(const thip_chain* chain, const Model* model,
+                                                              const Slots* slots, const double* pmc, int batch,
+                                                              const double* xin, const double* scene, double* out_all,
+                                                              int out_stride)
+{
+  const Slots& S = *slots;
+  const long long item = blockIdx.x;
+  if (item >= static_cast<long long>(S.n_units) * batch)
+    return;
+  const int b = static_cast<int>(item / S.n_units), u = static_cast<int>(item % S.n_units);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ thip_chain s_chain;
+  __shared__ double s_q[2][THIP_MAX_DOF];
+  __shared__ double s_ctr[kChunk + 1][THIP_MAX_SPHERES][3];
+  __shared__ double s_prim[THIP_MAX_PRIMS * 16];
+  __shared__ double s_w[kTvWaves];
+
+  const Model& M = *model;
+  const int n_prims = M.n_prims, D = S.D;
+  const bool single = S.coll_single != 0, cont = M.continuous != 0;
+  const double* gprims = scene + static_cast<long long>(b) * (n_prims > 0 ? n_prims : 1) * 16;
+  stage_chain_tv(s_chain, chain);
+  const int t0 = S.unit_t[u];
+  if (tid < 2 * D)
+  {
+    const int e = tid / D, j = tid % D;
+    const int t = (e == 1 && !single) ? t0 + 1 : t0;
+    s_q[e][j] = xin[(static_cast<long long>(b) * S.N + t) * D + j];
+  }
+  for (int w = tid; w < n_prims * 16; w += kTvBlock)
+    s_prim[w] = gprims[w];
+  __syncthreads();
+  const thip_chain& ch = s_chain;
+  const double* q0 = s_q[0];
+  const double* q1 = s_q[1];
+  // the unit's fixed ends (step-pair evaluators only; a DISCRETE term has no fixed waypoint)
+  const bool f0 = !single && S.coll_fixed[t0] != 0, f1 = !single && S.coll_fixed[t0 + 1] != 0;
+
+  // sub-states (DiscreteCollisionEvaluator / CastCollisionEvaluator, collision_terms.cpp:846-852)
+  const int cnt = single ? 1 : lvs_count(q0, q1, D, M.lvs);
+  const int n_sub = single ? 1 : (cont ? cnt - 1 : cnt);
+  const int last = cnt - 1;
+  const int n_sph = M.n_sph, n_groups = M.n_groups, PW = n_prims + n_sph;
+  const double buffer = M.buffer;
+
+  double lsum = 0.0;
+  for (int i0 = 0; i0 < n_sub; i0 += kChunk)
+  {
+    const int nc = min(kChunk, n_sub - i0);
+    const int nst = cont ? nc + 1 : nc;
+    // one FK per (state of the chunk, sphere-carrying link): world centres to LDS
+    for (int it = tid; it < nst * n_groups; it += kTvBlock)
+    {
+      const int j = it / n_groups, g = it - j * n_groups;
+      double q[THIP_MAX_DOF];
+      for (int k = 0; k < D; ++k)
+        q[k] = single ? q0[k] : linspaced(cnt, q0[k], q1[k], i0 + j);
+      Pose T;
+      chain_fk(ch, q, M.grp_link[g], T);
+      const int s0 = M.grp_s0[g], ng = M.grp_ns[g];
+      for (int e = 0; e < ng; ++e)
+      {
+        const int s = M.sph_order[s0 + e];
+        sphere_world_tv(T, M.center[s], s_ctr[j][s]);
+      }
+    }
+    __syncthreads();
+    const int n_scene_loc = n_sph * n_prims * nc;
+    const int n_loc = n_scene_loc + M.n_self_sph * nc;
+    for (int c = tid; c < n_loc; c += kTvBlock)
+    {
+      double dist, n[3], margin, coeff;
+      bool ok;  // the fixed-end rule keeps a contact of this candidate
+      if (c < n_scene_loc)
+      {
+        const int s = c % n_sph, r = c / n_sph, p = r % n_prims, il = r / n_prims, i = i0 + il;
+        const double* e = pmc ? pmc + 2 * (s * PW + p) : nullptr;
+        margin = e ? e[0] : M.margin;
+        coeff = e ? e[1] : M.coeff;
+        const double* prim = s_prim + 16 * p;
+        double pt[3];
+        int cct;  // CCType of the robot link: 1 Time0, 2 Time1, 3 Between
+        if (cont)
+        {
+          double ts = 0;
+          swept_sphere_prim_distance(s_ctr[il][s], s_ctr[il + 1][s], M.radius[s], prim, dist, n, pt, ts);
+          cct = (i == 0 && ts == 0.0) ? 1 : ((i + 1 == last && ts == 1.0) ? 2 : 3);
+        }
+        else
+        {
+          sphere_prim_distance(s_ctr[il][s], M.radius[s], prim, dist, n, pt);
+          cct = (i == 0) ? 1 : ((i == last) ? 2 : 3);
+        }
+        ok = !(f0 || f1) || (f0 && cct != 1) || (f1 && cct != 2);
+      }
+      else
+      {
+        const int r = c - n_scene_loc, j = r % M.n_self_sph, il = r / M.n_self_sph, i = i0 + il;
+        const int sa = M.self_sa[j], sb = M.self_sb[j];
+        const double* e = pmc ? pmc + 2 * (sa * PW + n_prims + sb) : nullptr;
+        margin = e ? e[0] : M.margin;
+        coeff = e ? e[1] : M.coeff;
+        const int il1 = cont ? il + 1 : il;
+        double pa[3], pb[3], ta, tb;
+        self_sphere_distance(s_ctr[il][sa], s_ctr[il1][sa], M.radius[sa], s_ctr[il][sb], s_ctr[il1][sb], M.radius[sb],
+                             cont, dist, n, pa, pb, ta, tb);
+        int cta, ctb;
+        if (cont)
+        {
+          cta = (i == 0 && ta == 0.0) ? 1 : ((i + 1 == last && ta == 1.0) ? 2 : 3);
+          ctb = (i == 0 && tb == 0.0) ? 1 : ((i + 1 == last && tb == 1.0) ? 2 : 3);
+        }
+        else
+          cta = ctb = (i == 0) ? 1 : ((i == last) ? 2 : 3);
+        ok = !(f0 || f1) || (f0 && (cta != 1 || ctb != 1)) || (f1 && (cta != 2 || ctb != 2));
+      }
+      // contactTest's hit within the pair's contact distance margin + buffer (a
+      // zero-coefficient pair reads margin -inf), then the evaluator's filter
+      const bool hit = dist < margin + buffer && ok;
+      lsum += hit ? fmax(margin - dist, 0.0) * coeff : 0.0;
+    }
+    __syncthreads();  // the next chunk overwrites the centres
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    lsum += __shfl_xor(lsum, off);
+  if (lane == 0)
+    s_w[wave] = lsum;
+  __syncthreads();
+  if (tid == 0)
+  {
+    double s = s_w[0];
+    for (int w = 1; w < kTvWaves; ++w)
+      s += s_w[w];
+    out_all[static_cast<long long>(b) * out_stride + S.coll_cost0 + S.unit_slot[u]] = s;
+  }
+}
+// Contact test FIRST / CLOSEST: the selection is per contactTest call and order
+// dependent, and coll_eval_kernel (term_eval.hip) already makes it; this kernel
+// only sums its records [batch][cap][W] = [t, link, prim, sphere, substate,
+// distance, ...] per unit.  One workgroup per (unit, problem), threads striding
+// over the problem's records.
+__global__ __launch_bounds__(kTvBlock) void coll_reduce_kernel(const Model* model, const Slots* slots, const double* pmc,
+                                                              int batch, const double* recs, const int* counts,
+                                                              int cap, int W, double* out_all, int out_stride)
+{
+  const Slots& S = *slots;
+  const long long item = blockIdx.x;
+  if (item >= static_cast<long long>(S.n_units) * batch)
+    return;
+  const int b = static_cast<int>(item / S.n_units), u = static_cast<int>(item % S.n_units);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ double s_w[kTvWaves];
+  const Model& M = *model;
+  const int PW = M.n_prims + M.n_sph, t0 = S.unit_t[u];
+  const int n = min(counts[b], cap);
+  const double* rec = recs + static_cast<long long>(b) * cap * W;
+  double lsum = 0.0;
+  for (int r = tid; r < n; r += kTvBlock)
+  {
+    const double* e = rec + static_cast<long long>(r) * W;
+    if (static_cast<int>(e[0]) != t0)
+      continue;
+    const int p = static_cast<int>(e[2]), s = static_cast<int>(e[3]);
+    const int col = p >= 0 ? p : M.n_prims + (-1 - p);
+    if (s < 0 || s >= M.n_sph || col < 0 || col >= PW)
+      continue;
+    const double* mc = pmc ? pmc + 2 * (s * PW + col) : nullptr;
+    const double margin = mc ? mc[0] : M.margin, coeff = mc ? mc[1] : M.coeff;
+    lsum += fmax(margin - e[5], 0.0) * coeff;
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    lsum += __shfl_xor(lsum, off);
+  if (lane == 0)
+    s_w[wave] = lsum;
+  __syncthreads();
+  if (tid == 0)
+  {
+    double s = s_w[0];
+    for (int w = 1; w < kTvWaves; ++w)
+      s += s_w[w];
+    out_all[static_cast<long long>(b) * out_stride + S.coll_cost0 + S.unit_slot[u]] = s;
+  }
+}
+}  // namespace tv
+}  // namespace thip
+
+using namespace thip;
+using namespace thip::tv;
+
+struct thip_terms
+{
+  int device = 0, batch = 0;
+  thip_problem_desc desc{};
+  Layout L{};  // the slot fields only
+  Slots slots{};
+  std::vector<thip_term_slot> table;
+  thip_problem_desc* d_desc = nullptr;
+  Slots* d_slots = nullptr;
+  Model* d_model = nullptr;
+  double* d_pair = nullptr;
+  double* d_tgt = nullptr;
+  double* d_scene = nullptr;
+  double* d_jpt = nullptr;
+  double* d_x = nullptr;  // staging of host trajectories
+  double* d_costs = nullptr;
+  double* d_viols = nullptr;
+  // contact test FIRST / CLOSEST: the device evaluator whose records are summed
+  // (thip_eval_collision: host trajectories in, host records out), and their staging
+  thip_eval* ev = nullptr;
+  std::vector<double> h_x, h_rec, h_scene;
+  std::vector<int> h_cnt;
+  double* d_rec = nullptr;
+  int* d_cnt = nullptr;
+  int rec_cap = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool uploaded = false;
+  double last_ms = -1.0;
+  std::string err;
+};
+
+static thread_local std::string g_terms_create_err;
+
+namespace
+{
+const char* const kHostLoop =
+    ": not lowered into the batched kernels -- evaluate such a problem on the host loop "
+    "(sco::BasicTrustRegionSQP, Cost::value / Constraint::violation)";
+
+// The descriptors thip_create accepts (thip_api.hip validate(), restated: the
+// same tests in the same order), refused with a reason before any device call.
+std::string validate_terms(const thip_problem_desc* d)
+{
+  if (d->abi_version != THIP_ABI_VERSION)
+    return "descriptor abi_version " + std::to_string(d->abi_version) + " != THIP_ABI_VERSION " +
+           std::to_string(THIP_ABI_VERSION);
+  const thip_chain& ch = d->chain;
+  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF)
+    return "n_dof out of range";
+  if (ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
+    return "n_links out of range";
+  if (d->n_steps < 2 || d->n_steps > THIP_MAX_STEPS)
+    return "n_steps must be in [2, " + std::to_string(THIP_MAX_STEPS) + "]" + kHostLoop;
+  for (int k = 1; k < ch.n_links; ++k)
+  {
+    const int ty = ch.joint_type[k];
+    if (ty < 0 || ty > 3)
+      return "bad joint type";
+    if (ty != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof))
+      return "bad joint dof index";
+    if (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k))
+      return "bad parent link (links must be in tree order, 0 <= parent[k] < k)";
+  }
+  if (d->n_fixed < 0 || d->n_fixed > THIP_MAX_STEPS)
+    return "n_fixed out of range";
+  {
+    std::vector<int> seen(static_cast<size_t>(d->n_steps), 0);
+    for (int f = 0; f < d->n_fixed; ++f)
+    {
+      const int t = d->fixed_steps[f];
+      if (t < 0 || t >= d->n_steps)
+        return "Fixed timestep index is outside the bounds of the initial trajectory.";
+      if (seen[static_cast<size_t>(t)]++)
+        return "duplicate fixed timestep";
+    }
+  }
+  if (d->n_cart < 0 || d->n_cart > THIP_MAX_CART)
+    return "n_cart out of range";
+  for (int k = 0; k < d->n_cart; ++k)
+  {
+    if (d->cart_step[k] < 0 || d->cart_step[k] >= d->n_steps)
+      return "CartPose timestep out of range";
+    if (d->cart_source_link[k] <= 0 || d->cart_source_link[k] >= ch.n_links)
+      return "CartPose source frame must be an active chain link";
+    if (d->cart_target_link[k] < 0 || d->cart_target_link[k] >= ch.n_links)
+      return "CartPose target link out of range (0: the static chain root)";
+  }
+  if (d->n_jvx < 0 || d->n_jvx > THIP_MAX_JVX)
+    return "n_jvx out of range";
+  for (int x = 0; x < d->n_jvx; ++x)
+  {
+    bool tol = false;
+    for (int j = 0; j < ch.n_dof; ++j)
+      tol = tol || std::fabs(d->jvx_upper_tols[x][j]) >= 1e-5 || std::fabs(d->jvx_lower_tols[x][j]) >= 1e-5;
+    if (!tol)
+      return "jvx terms are the tolerance forms: a term with zero tolerances goes in jv_*";
+  }
+  if (!thip_jdt_fused(d))
+    return std::string("JointAcc / JointJerk terms other than the fused JointAccEqCost (non-fused jdt)") + kHostLoop;
+  if (d->use_time != 0 || d->n_jvt != 0 || d->n_ttt != 0 || d->n_fixed_dofs != 0)
+    return std::string("time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs") +
+           kHostLoop;
+  if (d->coll_enabled && d->coll_contact_test != THIP_CONTACT_ALL && d->coll_contact_test != THIP_CONTACT_FIRST &&
+      d->coll_contact_test != THIP_CONTACT_CLOSEST)
+    return "coll_contact_test is not a THIP_CONTACT_* value";
+  if (d->n_coll_extra != 0)
+    return std::string("more than one collision term (coll_extra)") + kHostLoop;
+  if (d->n_jpos < 0 || d->n_jpos > THIP_MAX_JPOS)
+    return "n_jpos out of range";
+  for (int k = 0; k < d->n_jpos; ++k)
+    for (int j = 0; j < ch.n_dof; ++j)
+      if (!std::isfinite(d->jpos_coeffs[k][j]) || !std::isfinite(d->jpos_targets[k][j]) ||
+          !std::isfinite(d->jpos_upper_tols[k][j]) || !std::isfinite(d->jpos_lower_tols[k][j]))
+        return "JointPos coeffs / targets / tolerances must be finite";
+  if (d->coll_enabled)
+  {
+    if (d->n_spheres < 1 || d->n_spheres > THIP_MAX_SPHERES)
+      return "collision: n_spheres out of range";
+    for (int s = 0; s < d->n_spheres; ++s)
+      if (d->sphere_link[s] < 1 || d->sphere_link[s] >= ch.n_links || !(d->sphere_radius[s] >= 0))
+        return "collision: bad robot sphere";
+    if (d->n_prims < 0 || d->n_prims > THIP_MAX_PRIMS)
+      return std::string("collision: n_prims out of range (THIP_MAX_PRIMS)") + kHostLoop;
+    const int last = d->coll_last_step < 0 ? d->n_steps - 1 : d->coll_last_step;
+    if (d->coll_first_step < 0 || d->coll_first_step >= d->n_steps || last < d->coll_first_step || last >= d->n_steps)
+      return "collision: bad first/last step";
+    if (d->coll_continuous < 0 || d->coll_continuous > 2)
+      return "collision: coll_continuous must be 0 (LVS_DISCRETE), 1 (LVS_CONTINUOUS) or 2 (DISCRETE)";
+    const bool single = d->coll_continuous == 2;
+    if ((!single && !(d->coll_lvs > 0)) || !(d->coll_buffer >= 0))
+      return "collision: bad longest_valid_segment_length / buffer";
+    if (d->coll_n_fixed < 0 || d->coll_n_fixed > THIP_MAX_STEPS)
+      return "collision: coll_n_fixed out of range";
+    for (int t = d->coll_first_step; !single && t < last; ++t)
+    {
+      bool a = false, b = false;
+      for (int k = 0; k < d->coll_n_fixed; ++k)
+      {
+        a |= d->coll_fixed_steps[k] == t;
+        b |= d->coll_fixed_steps[k] == t + 1;
+      }
+      if (a && b)
+        return "Currently two adjacent fixed steps are not supported in collision term.";
+    }
+  }
+  for (int k = 0; k < d->n_cart; ++k)
+    if (d->cart_has_tol[k])
+      for (int i = 0; i < 6; ++i)
+        if (!(d->cart_lower_tol[k][i] <= d->cart_upper_tol[k][i]))
+          return "CartPoseErrCalculator: Inverted tolerance band - lower > upper at one or more indices";
+  if (d->coll_enabled && (d->coll_max_contacts < 0 || d->coll_max_contacts > THIP_MAX_CONTACTS))
+    return "collision: coll_max_contacts out of range";
+  if (d->coll_enabled)
+  {
+    std::vector<int> sa, sb, kp;
+    const std::string w = self_sphere_pairs(*d, sa, sb, kp);
+    if (!w.empty())
+      return w;
+  }
+  {
+    const std::string w = validate_coll_pairs(*d);
+    if (!w.empty())
+      return w;
+  }
+  // (the evaluator reads neither, but its domain is thip_create's)
+  if (!(d->sqp.max_time >= 0))
+    return "sqp.max_time must be >= 0 (DBL_MAX: no limit)";
+  if (!(d->sqp.trust_shrink_ratio > 0 && d->sqp.trust_shrink_ratio < 1) || !(d->sqp.min_trust_box_size > 0) ||
+      !(d->sqp.trust_box_size > 0))
+    return "sqp: need 0 < trust_shrink_ratio < 1, min_trust_box_size > 0 and trust_box_size > 0";
+  if (d->osqp.check_termination < 0 || d->osqp.max_iter < 1 || d->osqp.scaling < 0)
+    return "bad OSQP settings";
+  return "";
+}
+
+// thip_create's slot numbering (thip_api.hip:357-589) into Layout's slot fields,
+// the kernels' tables and the public slot table
+void number_slots(const thip_problem_desc& d, Layout& L, Slots& S, std::vector<thip_term_slot>& table)
+{
+  L.N = d.n_steps;
+  L.D = d.chain.n_dof;
+  L.n_cart = d.n_cart;
+  // JointVelTermInfo::hatch step clamping (problem_description.cpp:1228-1245)
+  auto jv_clamp = [&](int first, int last, int& f_out, int& l_out) {
+    if (last <= -1)
+      last = L.N - 1;
+    if ((L.N - 2) <= first)
+      first = L.N - 2;
+    if ((L.N - 1) <= last)
+      last = L.N - 1;
+    if (last == first)
+      last += 1;
+    if (last < first)
+      std::swap(first, last);
+    f_out = first;
+    l_out = last;
+  };
+  jv_clamp(d.jv_first_step, d.jv_last_step, L.jv_first, L.jv_last);
+  for (int x = 0; x < d.n_jvx; ++x)
+    jv_clamp(d.jvx_first_step[x], d.jvx_last_step[x], S.jvx_first[x], S.jvx_last[x]);
+  L.n_jvx = d.n_jvx;
+  auto zero_tol = [](double v) { return std::fabs(v) < 1e-5; };
+  L.jv_ineq = 0;
+  if (d.jv_enabled)
+    for (int j = 0; j < L.D; ++j)
+      if (!zero_tol(d.jv_upper_tols[j]) || !zero_tol(d.jv_lower_tols[j]))
+        L.jv_ineq = 1;
+  for (int k = 0; k < d.n_jpos; ++k)
+    for (int j = 0; j < L.D; ++j)
+      if (!zero_tol(d.jpos_upper_tols[k][j]) || !zero_tol(d.jpos_lower_tols[k][j]))
+        S.jpos_ineq[k] = 1;
+  std::vector<thip_term_slot> cost_tab, cnt_tab;
+  auto entry = [](int kind, int index, int unit, int is_cnt) {
+    thip_term_slot e;
+    e.kind = kind;
+    e.index = index;
+    e.unit = unit;
+    e.is_cnt = is_cnt;
+    return e;
+  };
+  int n_costs = 0, n_cnts = 0;
+  if (d.jv_enabled)
+  {
+    cost_tab.push_back(entry(THIP_TERM_JOINT_VEL, 0, -1, 0));
+    n_costs = 1;
+  }
+  // CartPose terms: cost terms first, then constraint terms, each in descriptor order
+  for (int pass = 0; pass < 2; ++pass)
+    for (int k = 0; k < d.n_cart; ++k)
+    {
+      if ((pass == 0) != (d.cart_is_cnt[k] == 0))
+        continue;
+      int nr = 0;
+      for (int i = 0; i < 6; ++i)
+      {
+        const double cf = (i < 3) ? d.cart_pos_coeffs[k][i] : d.cart_rot_coeffs[k][i - 3];
+        if (std::fabs(cf) > 1e-5)
+        {
+          S.row_comp[k][nr] = i;
+          S.row_w[k][nr] = cf;
+          nr++;
+        }
+      }
+      S.term_nrow[k] = nr;
+      S.term_slot[k] = (pass == 0) ? n_costs++ : n_cnts++;
+      (pass == 0 ? cost_tab : cnt_tab).push_back(entry(THIP_TERM_CART, k, -1, pass));
+    }
+  // JointPosTermInfo::hatch step clamping (problem_description.cpp:1097-1196)
+  L.n_jpos = d.n_jpos;
+  for (int k = 0; k < d.n_jpos; ++k)
+  {
+    int f = d.jpos_first_step[k], l = d.jpos_last_step[k];
+    if (l <= -1)
+      l = L.N - 1;
+    if ((L.N - 1) <= f)
+      f = L.N - 1;
+    if ((L.N - 1) <= l)
+      l = L.N - 1;
+    if (l < f)
+      std::swap(f, l);
+    f = std::max(f, 0);
+    S.jpos_first[k] = f;
+    S.jpos_last[k] = l;
+    if (!d.jpos_is_cnt[k])
+    {
+      S.jpos_slot[k] = n_costs++;
+      cost_tab.push_back(entry(THIP_TERM_JPOS, k, -1, 0));
+    }
+  }
+  for (int x = 0; x < d.n_jvx; ++x)
+    if (!d.jvx_is_cnt[x])
+    {
+      S.jvx_slot[x] = n_costs++;
+      cost_tab.push_back(entry(THIP_TERM_JVX, x, -1, 0));
+    }
+  L.n_jacc = d.n_jdt;
+  for (int k = 0; k < THIP_MAX_JDT; ++k)
+  {
+    L.jacc_slot[k] = (k < d.n_jdt) ? n_costs++ : -1;
+    if (k < d.n_jdt)
+      cost_tab.push_back(entry(THIP_TERM_JDT, k, -1, 0));
+  }
+  for (int k = 0; k < d.n_jpos; ++k)
+    if (d.jpos_is_cnt[k])
+    {
+      S.jpos_slot[k] = n_cnts++;
+      cnt_tab.push_back(entry(THIP_TERM_JPOS, k, -1, 1));
+    }
+  for (int x = 0; x < d.n_jvx; ++x)
+    if (d.jvx_is_cnt[x])
+    {
+      S.jvx_slot[x] = n_cnts++;
+      cnt_tab.push_back(entry(THIP_TERM_JVX, x, -1, 1));
+    }
+  // collision: one term per unit after the other costs (or constraints)
+  L.coll = d.coll_enabled ? 1 : 0;
+  L.coll_first = d.coll_first_step;
+  L.coll_last = (d.coll_last_step < 0) ? L.N - 1 : d.coll_last_step;
+  L.coll_single = (L.coll && d.coll_continuous == 2) ? 1 : 0;
+  if (L.coll_single)
+    L.coll_last += 1;
+  L.coll_cnt = (L.coll && d.coll_is_cnt) ? 1 : 0;
+  L.coll_cost0 = L.coll_cnt ? n_cnts : n_costs;
+  int n_units = 0;
+  for (int k = 0; L.coll && k < d.coll_n_fixed; ++k)
+    if (d.coll_fixed_steps[k] >= 0 && d.coll_fixed_steps[k] < L.N)
+      S.coll_fixed[d.coll_fixed_steps[k]] = 1;
+  for (int t = L.coll_first; L.coll && t < L.coll_last; ++t)
+    if (!(L.coll_single && S.coll_fixed[t]))
+    {
+      S.unit_t[n_units] = t;
+      S.unit_slot[n_units] = n_units;
+      (L.coll_cnt ? cnt_tab : cost_tab).push_back(entry(THIP_TERM_COLL, n_units, t, L.coll_cnt));
+      n_units++;
+    }
+  if (L.coll)
+    (L.coll_cnt ? n_cnts : n_costs) += n_units;
+  L.n_costs = n_costs;
+  L.n_cnts = n_cnts;
+
+  S.N = L.N;
+  S.D = L.D;
+  S.n_costs = L.n_costs;
+  S.n_cnts = L.n_cnts;
+  S.jv_eq = (d.jv_enabled && !L.jv_ineq) ? 1 : 0;
+  S.jv_ineq = L.jv_ineq;
+  S.jv_first = L.jv_first;
+  S.jv_last = L.jv_last;
+  S.n_jacc = L.n_jacc;
+  for (int k = 0; k < THIP_MAX_JDT; ++k)
+    S.jacc_slot[k] = L.jacc_slot[k];
+  S.n_cart = L.n_cart;
+  S.n_jpos = L.n_jpos;
+  S.n_jvx = L.n_jvx;
+  S.coll = L.coll;
+  S.coll_single = L.coll_single;
+  S.coll_cnt = L.coll_cnt;
+  S.coll_cost0 = L.coll_cost0;
+  S.n_units = n_units;
+  table = cost_tab;
+  table.insert(table.end(), cnt_tab.begin(), cnt_tab.end());
+}
+
+int tfail(thip_terms* t, const std::string& m)
+{
+  t->err = m;
+  return THIP_E_INVALID;
+}
+int thipfail(thip_terms* t, const char* what, hipError_t e)
+{
+  t->err = std::string(what) + ": " + hipGetErrorString(e);
+  return THIP_E_HIP;
+}
+
+int run_on_device(thip_terms* t, const double* d_x, double* costs, double* viols)
+{
+  const size_t B = static_cast<size_t>(t->batch);
+  const Slots& S = t->slots;
+  hipError_t e;
+  if ((e = hipEventRecord(t->ev0, t->stream)) != hipSuccess)
+    return thipfail(t, "hipEventRecord", e);
+  hipLaunchKernelGGL(term_values_kernel, dim3(t->batch), dim3(kTvBlock), 0, t->stream, t->d_desc, t->d_slots, t->batch,
+                     d_x, t->d_tgt, t->d_jpt, t->d_costs, t->d_viols);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return thipfail(t, "term_values_kernel launch", e);
+  if (S.coll && S.n_units > 0 && t->ev)
+  {
+    // FIRST / CLOSEST: coll_eval_kernel's records of every problem, then their per-unit sums
+    const size_t nx = B * S.N * S.D;
+    const int W = 8 + 2 * S.D + 1;
+    t->h_x.resize(nx);
+    t->h_cnt.assign(B, 0);
+    if ((e = hipMemcpyAsync(t->h_x.data(), d_x, nx * sizeof(double), hipMemcpyDeviceToHost, t->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(t->stream)) != hipSuccess)
+      return thipfail(t, "hipMemcpy(x)", e);
+    for (int attempt = 0; attempt < 2; ++attempt)
+    {
+      t->h_rec.resize(B * static_cast<size_t>(t->rec_cap) * W);
+      if (thip_eval_collision(t->ev, 0, t->h_x.data(), t->h_rec.data(), t->rec_cap, t->h_cnt.data()) != THIP_OK)
+        return tfail(t, std::string("thip_eval_collision: ") + thip_eval_last_error(t->ev));
+      const int mx = *std::max_element(t->h_cnt.begin(), t->h_cnt.end());
+      if (mx <= t->rec_cap)
+        break;
+      t->rec_cap = mx;  // a problem had more contacts than the staging holds: once more with room for all
+      hipFree(t->d_rec);
+      t->d_rec = nullptr;
+    }
+    // a record names a robot sphere and a primitive or a second sphere: anything else is an
+    // error here, not a contact to skip (the kernel's own range test only guards its reads)
+    for (size_t b = 0; b < B; ++b)
+      for (int r = 0; r < t->h_cnt[b]; ++r)
+      {
+        const double* e = t->h_rec.data() + (b * static_cast<size_t>(t->rec_cap) + r) * W;
+        const int p = static_cast<int>(e[2]), s = static_cast<int>(e[3]);
+        if (s < 0 || s >= t->desc.n_spheres || (p >= 0 ? p >= t->desc.n_prims : -1 - p >= t->desc.n_spheres))
+          return tfail(t, "thip_eval_collision returned a contact record with sphere " + std::to_string(s) +
+                              " / other " + std::to_string(p) + " out of range");
+      }
+    if (!t->d_rec && (e = hipMalloc(&t->d_rec, B * static_cast<size_t>(t->rec_cap) * W * sizeof(double))) != hipSuccess)
+      return thipfail(t, "hipMalloc(contact records)", e);
+    if ((e = hipMemcpyAsync(t->d_rec, t->h_rec.data(), t->h_rec.size() * sizeof(double), hipMemcpyHostToDevice,
+                            t->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(t->d_cnt, t->h_cnt.data(), B * sizeof(int), hipMemcpyHostToDevice, t->stream)) != hipSuccess)
+      return thipfail(t, "hipMemcpy(contact records)", e);
+    hipLaunchKernelGGL(coll_reduce_kernel, dim3(static_cast<unsigned>(B * S.n_units)), dim3(kTvBlock), 0, t->stream,
+                       t->d_model, t->d_slots, t->d_pair, t->batch, t->d_rec, t->d_cnt, t->rec_cap, W,
+                       S.coll_cnt ? t->d_viols : t->d_costs, std::max(S.coll_cnt ? S.n_cnts : S.n_costs, 1));
+    if ((e = hipGetLastError()) != hipSuccess)
+      return thipfail(t, "coll_reduce_kernel launch", e);
+  }
+  else if (S.coll && S.n_units > 0)
+  {
+    hipLaunchKernelGGL(coll_values_kernel, dim3(static_cast<unsigned>(B * S.n_units)), dim3(kTvBlock), 0, t->stream,
+                       &t->d_desc->chain, t->d_model, t->d_slots, t->d_pair, t->batch, d_x, t->d_scene,
+                       S.coll_cnt ? t->d_viols : t->d_costs, std::max(S.coll_cnt ? S.n_cnts : S.n_costs, 1));
+    if ((e = hipGetLastError()) != hipSuccess)
+      return thipfail(t, "coll_values_kernel launch", e);
+  }
+  if ((e = hipEventRecord(t->ev1, t->stream)) != hipSuccess)
+    return thipfail(t, "hipEventRecord", e);
+  if ((S.n_costs > 0 && costs &&
+       (e = hipMemcpyAsync(costs, t->d_costs, B * S.n_costs * sizeof(double), hipMemcpyDeviceToHost, t->stream)) !=
+           hipSuccess) ||
+      (S.n_cnts > 0 && viols &&
+       (e = hipMemcpyAsync(viols, t->d_viols, B * S.n_cnts * sizeof(double), hipMemcpyDeviceToHost, t->stream)) !=
+           hipSuccess) ||
+      (e = hipStreamSynchronize(t->stream)) != hipSuccess)
+    return thipfail(t, "term value kernels", e);
+  float ms = -1.0f;
+  t->last_ms = hipEventElapsedTime(&ms, t->ev0, t->ev1) == hipSuccess ? static_cast<double>(ms) : -1.0;
+  return THIP_OK;
+}
+
+int upload_inputs(thip_terms* t, const double* tgt, const double* scene, hipMemcpyKind kind, const char* who)
+{
+  if (!t)
+    return THIP_E_INVALID;
+  const thip_problem_desc& d = t->desc;
+  const bool need_scene = d.coll_enabled && d.n_prims > 0;
+  if (d.n_cart > 0 && !tgt)
+    return tfail(t, std::string(who) + ": cart_targets required when n_cart > 0");
+  if (need_scene && !scene)
+    return tfail(t, std::string(who) + ": scene required when the collision term has primitives");
+  const size_t B = static_cast<size_t>(t->batch);
+  hipError_t e;
+  if ((e = hipSetDevice(t->device)) != hipSuccess)
+    return thipfail(t, "hipSetDevice", e);
+  if (d.n_cart > 0 && (e = hipMemcpyAsync(t->d_tgt, tgt, B * d.n_cart * 12 * sizeof(double), kind, t->stream)) != hipSuccess)
+    return thipfail(t, "hipMemcpy(cart_targets)", e);
+  if (need_scene &&
+      (e = hipMemcpyAsync(t->d_scene, scene, B * d.n_prims * 16 * sizeof(double), kind, t->stream)) != hipSuccess)
+    return thipfail(t, "hipMemcpy(scene)", e);
+  if ((e = hipStreamSynchronize(t->stream)) != hipSuccess)
+    return thipfail(t, "hipStreamSynchronize", e);
+  if (t->ev)
+  {
+    // the FIRST / CLOSEST route's evaluator takes host arrays; it reads no CartPose target
+    const double* hs = scene;
+    if (need_scene && kind == hipMemcpyDeviceToDevice)
+    {
+      t->h_scene.resize(B * d.n_prims * 16);
+      if ((e = hipMemcpy(t->h_scene.data(), t->d_scene, t->h_scene.size() * sizeof(double), hipMemcpyDeviceToHost)) !=
+          hipSuccess)
+        return thipfail(t, "hipMemcpy(scene)", e);
+      hs = t->h_scene.data();
+    }
+    const std::vector<double> zeros(B * std::max(d.n_cart, 1) * 12, 0.0);
+    if (thip_eval_upload(t->ev, zeros.data(), hs) != THIP_OK)
+      return tfail(t, std::string("thip_eval_upload: ") + thip_eval_last_error(t->ev));
+  }
+  t->uploaded = true;
+  return THIP_OK;
+}
+
+int upload_jpt(thip_terms* t, const double* jpt, hipMemcpyKind kind, const char* who)
+{
+  if (!t)
+    return THIP_E_INVALID;
+  if (!jpt)
+    return tfail(t, std::string(who) + ": null jpos_targets");
+  if (t->desc.n_jpos == 0)
+    return THIP_OK;
+  hipError_t e;
+  if ((e = hipSetDevice(t->device)) != hipSuccess)
+    return thipfail(t, "hipSetDevice", e);
+  const size_t n = static_cast<size_t>(t->batch) * t->desc.n_jpos * t->desc.chain.n_dof;
+  if ((e = hipMemcpyAsync(t->d_jpt, jpt, n * sizeof(double), kind, t->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(t->stream)) != hipSuccess)
+    return thipfail(t, "hipMemcpy(jpos_targets)", e);
+  return THIP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int thip_sizeof_term_slot(void) { return static_cast<int>(sizeof(thip_term_slot)); }
+
+int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip_terms** out)
+{
+  if (out)
+    *out = nullptr;
+  if (!desc || !out || batch <= 0)
+  {
+    g_terms_create_err = "thip_terms_create: null argument or batch <= 0";
+    return THIP_E_INVALID;
+  }
+  auto reject = [](const std::string& m) {
+    g_terms_create_err = "thip_terms_create: " + m;
+    return THIP_E_INVALID;
+  };
+  {
+    const std::string why = validate_terms(desc);
+    if (!why.empty())
+      return reject(why);
+  }
+  auto* t = new thip_terms();
+  t->device = device;
+  t->batch = batch;
+  t->desc = *desc;
+  if (!t->desc.chain.is_tree)  // serial chain: parent[] is not read from the caller
+    for (int k = 0; k < THIP_MAX_LINKS; ++k)
+      t->desc.chain.parent[k] = k > 0 ? k - 1 : 0;
+  const thip_problem_desc& d = t->desc;
+  number_slots(d, t->L, t->slots, t->table);
+  const Slots& S = t->slots;
+  if (static_cast<long long>(std::max(S.n_units, 1)) * batch > INT_MAX)
+  {
+    delete t;
+    return reject("batch * collision units exceeds the grid");
+  }
+  Model md{};
+  std::vector<double> ptab;
+  if (d.coll_enabled)
+  {
+    std::vector<int> order, ssa, ssb, skp;
+    self_sphere_pairs(d, ssa, ssb, skp);
+    for (int s = 0; s < d.n_spheres; ++s)
+      order.push_back(s);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d.sphere_link[a] < d.sphere_link[b]; });
+    md.n_sph = d.n_spheres;
+    md.n_prims = d.n_prims;
+    for (size_t k = 0; k < order.size(); ++k)
+    {
+      md.sph_order[k] = order[k];
+      const int link = d.sphere_link[order[k]];
+      if (md.n_groups == 0 || md.grp_link[md.n_groups - 1] != link)
+      {
+        md.grp_link[md.n_groups] = link;
+        md.grp_s0[md.n_groups] = static_cast<int>(k);
+        md.grp_ns[md.n_groups] = 0;
+        md.n_groups++;
+      }
+      md.grp_ns[md.n_groups - 1]++;
+    }
+    md.n_self_sph = static_cast<int>(ssa.size());
+    for (size_t j = 0; j < ssa.size(); ++j)
+    {
+      md.self_sa[j] = ssa[j];
+      md.self_sb[j] = ssb[j];
+    }
+    for (int s = 0; s < d.n_spheres; ++s)
+    {
+      md.radius[s] = d.sphere_radius[s];
+      for (int i = 0; i < 3; ++i)
+        md.center[s][i] = d.sphere_center[s][i];
+    }
+    md.continuous = d.coll_continuous == 1;
+    md.lvs = d.coll_lvs;
+    md.margin = d.coll_margin;
+    md.coeff = d.coll_coeff;
+    md.buffer = d.coll_buffer;
+    coll_pair_table(d, 0, ptab);
+  }
+  auto hfail = [&](const char* what, hipError_t e) {
+    g_terms_create_err = std::string("thip_terms_create: ") + what + ": " + hipGetErrorString(e);
+    thip_terms_destroy(t);
+    return THIP_E_HIP;
+  };
+  hipError_t e;
+  if ((e = hipSetDevice(device)) != hipSuccess)
+    return hfail("hipSetDevice", e);
+  const size_t B = static_cast<size_t>(batch), D = static_cast<size_t>(S.D);
+  const size_t n_tgt = B * std::max(d.n_cart, 1) * 12, n_scene = B * std::max(d.n_prims, 1) * 16;
+  const size_t per_jpt = std::max(d.n_jpos, 1) * D;
+  const size_t n_c = B * std::max(S.n_costs, 1), n_v = B * std::max(S.n_cnts, 1);
+  if ((e = hipMalloc(&t->d_desc, sizeof(thip_problem_desc))) != hipSuccess ||
+      (e = hipMalloc(&t->d_slots, sizeof(Slots))) != hipSuccess ||
+      (e = hipMalloc(&t->d_model, sizeof(Model))) != hipSuccess ||
+      (e = hipMalloc(&t->d_tgt, n_tgt * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc(&t->d_scene, n_scene * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc(&t->d_jpt, B * per_jpt * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc(&t->d_x, B * S.N * D * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc(&t->d_costs, n_c * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc(&t->d_viols, n_v * sizeof(double))) != hipSuccess ||
+      (!ptab.empty() && (e = hipMalloc(&t->d_pair, ptab.size() * sizeof(double))) != hipSuccess))
+    return hfail("hipMalloc", e);
+  if ((e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess)
+    return hfail("hipStreamCreate", e);
+  if ((e = hipEventCreate(&t->ev0)) != hipSuccess || (e = hipEventCreate(&t->ev1)) != hipSuccess)
+    return hfail("hipEventCreate", e);
+  // every problem starts with the descriptor's JointPos targets
+  std::vector<double> jpt(B * per_jpt, 0.0);
+  for (size_t b = 0; b < B; ++b)
+    for (int k = 0; k < d.n_jpos; ++k)
+      for (size_t j = 0; j < D; ++j)
+        jpt[b * per_jpt + k * D + j] = d.jpos_targets[k][j];
+  if ((e = hipMemcpyAsync(t->d_desc, &t->desc, sizeof(thip_problem_desc), hipMemcpyHostToDevice, t->stream)) !=
+          hipSuccess ||
+      (e = hipMemcpyAsync(t->d_slots, &t->slots, sizeof(Slots), hipMemcpyHostToDevice, t->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(t->d_model, &md, sizeof(Model), hipMemcpyHostToDevice, t->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(t->d_jpt, jpt.data(), jpt.size() * sizeof(double), hipMemcpyHostToDevice, t->stream)) !=
+          hipSuccess ||
+      (!ptab.empty() && (e = hipMemcpyAsync(t->d_pair, ptab.data(), ptab.size() * sizeof(double),
+                                            hipMemcpyHostToDevice, t->stream)) != hipSuccess) ||
+      (e = hipMemsetAsync(t->d_tgt, 0, n_tgt * sizeof(double), t->stream)) != hipSuccess ||
+      (e = hipMemsetAsync(t->d_scene, 0, n_scene * sizeof(double), t->stream)) != hipSuccess ||
+      (e = hipMemsetAsync(t->d_costs, 0, n_c * sizeof(double), t->stream)) != hipSuccess ||
+      (e = hipMemsetAsync(t->d_viols, 0, n_v * sizeof(double), t->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(t->stream)) != hipSuccess)
+    return hfail("hipMemcpy", e);
+  // nothing to upload: the evaluator is ready
+  t->uploaded = d.n_cart == 0 && !(d.coll_enabled && d.n_prims > 0);
+  if (d.coll_enabled && d.coll_contact_test != THIP_CONTACT_ALL)
+  {
+    if (thip_eval_create(device, &t->desc, batch, &t->ev) != THIP_OK)
+    {
+      g_terms_create_err = std::string("thip_terms_create: ") + thip_eval_last_error(nullptr);
+      thip_terms_destroy(t);
+      return THIP_E_HIP;
+    }
+    t->rec_cap = 256;
+    if ((e = hipMalloc(&t->d_cnt, B * sizeof(int))) != hipSuccess)
+      return hfail("hipMalloc", e);
+    if (t->uploaded && thip_eval_upload(t->ev, nullptr, nullptr) != THIP_OK)
+    {
+      g_terms_create_err = std::string("thip_terms_create: ") + thip_eval_last_error(t->ev);
+      thip_terms_destroy(t);
+      return THIP_E_HIP;
+    }
+  }
+  *out = t;
+  return THIP_OK;
+}
+
+int thip_terms_slot_table(const thip_problem_desc* desc, thip_term_slot* out, int cap, int* n_costs, int* n_cnts)
+{
+  if (!desc || cap < 0 || (cap > 0 && !out))
+  {
+    g_terms_create_err = "thip_terms_slot_table: bad arguments";
+    return THIP_E_INVALID;
+  }
+  const std::string why = validate_terms(desc);
+  if (!why.empty())
+  {
+    g_terms_create_err = "thip_terms_slot_table: " + why;
+    return THIP_E_INVALID;
+  }
+  Layout L{};
+  Slots S{};
+  std::vector<thip_term_slot> table;
+  number_slots(*desc, L, S, table);
+  if (n_costs)
+    *n_costs = L.n_costs;
+  if (n_cnts)
+    *n_cnts = L.n_cnts;
+  for (size_t k = 0; k < table.size() && k < static_cast<size_t>(cap); ++k)
+    out[k] = table[k];
+  return THIP_OK;
+}
+
+int thip_terms_counts(const thip_terms* t, int* n_costs, int* n_cnts)
+{
+  if (!t)
+    return THIP_E_INVALID;
+  if (n_costs)
+    *n_costs = t->slots.n_costs;
+  if (n_cnts)
+    *n_cnts = t->slots.n_cnts;
+  return THIP_OK;
+}
+
+int thip_terms_slots(const thip_terms* t, thip_term_slot* out)
+{
+  if (!t || !out)
+    return THIP_E_INVALID;
+  for (size_t k = 0; k < t->table.size(); ++k)
+    out[k] = t->table[k];
+  return THIP_OK;
+}
+
+int thip_terms_upload(thip_terms* t, const double* cart_targets, const double* scene)
+{
+  return upload_inputs(t, cart_targets, scene, hipMemcpyHostToDevice, "thip_terms_upload");
+}
+
+int thip_terms_upload_device(thip_terms* t, const double* d_cart_targets, const double* d_scene)
+{
+  return upload_inputs(t, d_cart_targets, d_scene, hipMemcpyDeviceToDevice, "thip_terms_upload_device");
+}
+
+int thip_terms_upload_joint_targets(thip_terms* t, const double* jpos_targets)
+{
+  return upload_jpt(t, jpos_targets, hipMemcpyHostToDevice, "thip_terms_upload_joint_targets");
+}
+
+int thip_terms_upload_joint_targets_device(thip_terms* t, const double* d_jpos_targets)
+{
+  return upload_jpt(t, d_jpos_targets, hipMemcpyDeviceToDevice, "thip_terms_upload_joint_targets_device");
+}
+
+int thip_terms_run(thip_terms* t, const double* x, double* costs, double* viols)
+{
+  if (!t)
+    return THIP_E_INVALID;
+  if (!x || (t->slots.n_costs > 0 && !costs) || (t->slots.n_cnts > 0 && !viols))
+    return tfail(t, "thip_terms_run: null x / costs / viols");
+  if (!t->uploaded)
+    return tfail(t, "thip_terms_run: thip_terms_upload first");
+  hipError_t e;
+  if ((e = hipSetDevice(t->device)) != hipSuccess)
+    return thipfail(t, "hipSetDevice", e);
+  const size_t n = static_cast<size_t>(t->batch) * t->slots.N * t->slots.D;
+  if ((e = hipMemcpyAsync(t->d_x, x, n * sizeof(double), hipMemcpyHostToDevice, t->stream)) != hipSuccess)
+    return thipfail(t, "hipMemcpy(x)", e);
+  return run_on_device(t, t->d_x, costs, viols);
+}
+
+int thip_terms_run_device(thip_terms* t, const double* d_x, double* costs, double* viols)
+{
+  if (!t)
+    return THIP_E_INVALID;
+  if (!d_x || (t->slots.n_costs > 0 && !costs) || (t->slots.n_cnts > 0 && !viols))
+    return tfail(t, "thip_terms_run_device: null d_x / costs / viols");
+  if (!t->uploaded)
+    return tfail(t, "thip_terms_run_device: thip_terms_upload first");
+  hipError_t e;
+  if ((e = hipSetDevice(t->device)) != hipSuccess)
+    return thipfail(t, "hipSetDevice", e);
+  return run_on_device(t, d_x, costs, viols);
+}
+
+double thip_terms_last_ms(thip_terms* t) { return t ? t->last_ms : -1.0; }
+
+void thip_terms_destroy(thip_terms* t)
+{
+  if (!t)
+    return;
+  hipSetDevice(t->device);
+  if (t->stream)
+    hipStreamSynchronize(t->stream);
+  hipFree(t->d_desc);
+  hipFree(t->d_slots);
+  hipFree(t->d_model);
+  hipFree(t->d_pair);
+  hipFree(t->d_tgt);
+  hipFree(t->d_scene);
+  hipFree(t->d_jpt);
+  hipFree(t->d_x);
+  hipFree(t->d_costs);
+  hipFree(t->d_viols);
+  hipFree(t->d_rec);
+  hipFree(t->d_cnt);
+  thip_eval_destroy(t->ev);
+  if (t->ev0)
+    hipEventDestroy(t->ev0);
+  if (t->ev1)
+    hipEventDestroy(t->ev1);
+  if (t->stream)
+    hipStreamDestroy(t->stream);
+  delete t;
+}
+
+const char* thip_terms_last_error(thip_terms* t) { return t ? t->err.c_str() : g_terms_create_err.c_str(); }
+
+}  // extern "C"

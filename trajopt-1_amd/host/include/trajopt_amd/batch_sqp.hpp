@@ -9,6 +9,7 @@
 
 #include "trajopt_amd/check_trajectory.hpp"
 #include "trajopt_amd/problem_description.hpp"
+#include "trajopt_amd/term_evaluator.hpp"
 
 namespace trajopt
 {
@@ -38,13 +39,24 @@ public:
   void submit();
   std::vector<sco::OptResults> collect();
   // submit() for another batch of the same structure and size on this context
-  // (its device workspace is reused; collect() the previous batch first)
+  // (its device workspace is reused; collect() the previous batch first).  On a
+  // batch built from TrajOptProbs, cost_vals / cnt_viols keep the order and
+  // evaluate() the names of those first problems' term objects: the structure is
+  // the same, so the order is, but names that differ per problem are not updated.
   void submit(std::vector<LoweredProblem> probs);
   // checkTrajectory on the last solve's trajectories where they lie on the device
   // (thip_device_x: no round trip), one report per problem.  Waits for the solve.
   // A host-loop batch keeps no device trajectories: check its results with
   // trajopt::checkTrajectory.
   std::vector<TrajectoryCheckReport> checkResults(const CollisionCheckConfig& config = CollisionCheckConfig());
+  // Every cost's value and every constraint's violation of the batch's problems at
+  // arbitrary trajectories (seeds, upsampled results, another planner's output), one
+  // result per problem: the batch's own TermEvaluator.  collect() fills
+  // OptResults::cost_vals / cnt_viols with the same evaluator from the trajectories
+  // still on the device: in getCosts() / getConstraints() order for a batch built
+  // from TrajOptProbs, in kernel slot order for one built from LoweredProblems.
+  // A host-loop batch has its values from the host loop itself.
+  std::vector<TrajOptResult> evaluate(const std::vector<TrajArray>& trajs);
   // HIP-event duration of the last fused launch (ms).
   double lastKernelMs() const;
   // Per-QP records of the next optimize() (thip_debug_trace, THIP_TRACE_W doubles each).
@@ -79,6 +91,7 @@ private:
   std::vector<sco::OptResults> optimizeHostLoops();
   std::vector<LoweredProblem> probs_;
   struct thip_ctx* ctx_ = nullptr;
+  std::unique_ptr<TermEvaluator> terms_;  // created next to ctx_ (init)
   int trace_cap_ = 0;
   std::vector<TrajOptProb::Ptr> generic_;  // host-loop batch
   int device_ = 0;

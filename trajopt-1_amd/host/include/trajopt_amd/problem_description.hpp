@@ -358,8 +358,17 @@ public:
 
   // a built-in hatch() adds its lowered terms through these (counted), a user
   // TermInfo through addCost / addConstraint (not lowered)
-  void addLoweredCost(sco::Cost::Ptr c);
-  void addLoweredConstraint(sco::Constraint::Ptr c);
+  // kind / index / unit: the term's place in the descriptor (THIP_TERM_* of
+  // trajopt_hip.h, index within the kind, waypoint of a collision unit), the
+  // record termSlotMap() matches kernel slots to term objects with
+  void addLoweredCost(sco::Cost::Ptr c, int kind = -1, int index = -1, int unit = -1);
+  void addLoweredConstraint(sco::Constraint::Ptr c, int kind = -1, int index = -1, int unit = -1);
+  struct LoweredRecord
+  {
+    const void* obj;
+    int kind, index, unit, is_cnt;
+  };
+  const std::vector<LoweredRecord>& loweredRecords() const { return lowered_records_; }
   // every cost and constraint lowered into desc() (the batched kernel runs it)
   bool lowerable() const;
   std::string unloweredTerms() const;  // names of the terms the kernel does not run
@@ -382,6 +391,7 @@ private:
   Environment::ConstPtr env_;
   VarArray traj_vars_, joint_vars_;
   std::vector<const void*> lowered_;  // the lowered Cost / Constraint objects
+  std::vector<LoweredRecord> lowered_records_;
   std::shared_ptr<DeviceTermEvaluator> device_terms_;
 };
 

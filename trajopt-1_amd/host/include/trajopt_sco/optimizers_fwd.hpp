@@ -26,7 +26,7 @@ struct OptResults
   DblVec x;
   OptStatus status{ INVALID };
   double total_cost{ 0 };
-  DblVec cost_vals;  // the batched kernel reports totals only (empty there)
+  DblVec cost_vals;  // per term, getCosts() / getConstraints() order (the batched path: trajopt::TermEvaluator)
   DblVec cnt_viols;
   int n_func_evals{ 0 }, n_qp_solves{ 0 };
   int n_sqp_iters{ 0 };

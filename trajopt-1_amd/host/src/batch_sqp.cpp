@@ -221,6 +221,29 @@ void BatchTrustRegionSQP::init(int device)
   const int rc = thip_create(device, &d0, static_cast<int>(probs_.size()), &ctx_);
   if (rc != THIP_OK)
     throw std::runtime_error(std::string("thip_create: ") + thip_last_error(nullptr));
+  // the per-term evaluator of the batch (collect() and evaluate()): with the term
+  // objects' order and names when the batch was built from TrajOptProbs
+  try
+  {
+    if (source_.size() == probs_.size())
+      terms_ = std::make_unique<TermEvaluator>(source_, device);
+    else
+      terms_ = std::make_unique<TermEvaluator>(probs_, device);
+  }
+  catch (...)
+  {
+    thip_destroy(ctx_);
+    ctx_ = nullptr;
+    throw;
+  }
+}
+
+std::vector<TrajOptResult> BatchTrustRegionSQP::evaluate(const std::vector<TrajArray>& trajs)
+{
+  if (!generic_.empty())
+    throw std::runtime_error("BatchTrustRegionSQP::evaluate: a host-loop batch evaluates its terms on the host loop "
+                             "(Cost::value / Constraint::violation)");
+  return terms_->evaluate(trajs);
 }
 
 BatchTrustRegionSQP::~BatchTrustRegionSQP() { thip_destroy(ctx_); }
@@ -322,6 +345,7 @@ void BatchTrustRegionSQP::submit(std::vector<LoweredProblem> probs)
   }
   probs_ = std::move(probs);
   source_.clear();
+  terms_->upload(probs_);  // (the term objects of the first batch keep giving the order and the names)
   submit();
 }
 
@@ -334,6 +358,8 @@ std::vector<sco::OptResults> BatchTrustRegionSQP::collect()
   std::vector<double> x(static_cast<std::size_t>(B) * N * D);
   std::vector<thip_result> res(static_cast<std::size_t>(B));
   check(thip_download(ctx_, x.data(), res.data()), "thip_download");
+  // the per-term values at the returned trajectories, read where they lie on the device
+  const std::vector<TrajOptResult> terms = terms_->evaluateDevice(thip_device_x(ctx_));
   std::vector<sco::OptResults> out(static_cast<std::size_t>(B));
   for (int b = 0; b < B; ++b)
   {
@@ -348,6 +374,8 @@ std::vector<sco::OptResults> BatchTrustRegionSQP::collect()
     o.n_admm_iters = r.n_admm_iters;
     o.max_cnt_viol = r.max_cnt_viol;
     o.flags = r.flags;
+    o.cost_vals = terms[static_cast<std::size_t>(b)].cost_vals;
+    o.cnt_viols = terms[static_cast<std::size_t>(b)].cnt_viols;
   }
   return out;
 }
@@ -607,8 +635,23 @@ bool TrajOptProb::solveNative(const sco::BasicTrustRegionSQPParameters& param, c
   LoweredProblem lp = lowered();
   lp.init = x0;
   copyParams(param, lp.desc.sqp);
+  const thip_problem_desc lp_structure = lp.desc;
   BatchTrustRegionSQP batch(std::vector<LoweredProblem>{ std::move(lp) }, device);
   results = batch.optimize()[0];
+  // the batch of one was built from the lowered form: its values are in kernel slot
+  // order; results() promises getCosts() / getConstraints() order
+  {
+    int nc = 0, nv = 0;
+    const std::vector<thip_term_slot> table = termSlotTable(lp_structure, nc, nv);
+    const TermSlotMap m = termSlotMap(*this, table, nc, nv);
+    DblVec cv(results.cost_vals.size()), vv(results.cnt_viols.size());
+    for (std::size_t s = 0; s < cv.size(); ++s)
+      cv[static_cast<std::size_t>(m.cost_pos[s])] = results.cost_vals[s];
+    for (std::size_t s = 0; s < vv.size(); ++s)
+      vv[static_cast<std::size_t>(m.cnt_pos[s])] = results.cnt_viols[s];
+    results.cost_vals = cv;
+    results.cnt_viols = vv;
+  }
   return true;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "trajopt_amd/batch_sqp.hpp"
+#include "trajopt_amd/term_evaluator.hpp"
 
 namespace
 {
@@ -141,6 +142,111 @@ int thost_check_json_batch(const char* const* json_texts, int batch, const doubl
   }
 }
 
+int thost_eval_json_batch(const char* const* json_texts, int batch, const double* scenes, int n_prims,
+                          const double* trajectories, int route, int device, int* n_costs, int* n_cnts,
+                          double* cost_vals, double* cnt_viols, char* names, int names_len, int* slot_map, char* err,
+                          int err_len)
+{
+  try
+  {
+    if (!json_texts || batch <= 0 || route < THOST_EVAL_DEVICE || route > THOST_EVAL_NAMES)
+      throw std::runtime_error("thost_eval_json_batch: null argument, batch <= 0 or bad route");
+    if (route != THOST_EVAL_NAMES && !trajectories)
+      throw std::runtime_error("thost_eval_json_batch: null trajectories");
+    std::vector<trajopt::TrajOptProb::Ptr> probs;
+    std::vector<trajopt::TrajArray> trajs;
+    const double* x = trajectories;
+    for (int b = 0; b < batch; ++b)
+    {
+      probs.push_back(construct(json_texts[b], scenes ? scenes + static_cast<std::size_t>(b) * n_prims * 16 : nullptr,
+                                n_prims));
+      probs.back()->device = device;
+      const int N = probs.back()->GetNumSteps(), D = probs.back()->GetNumDOF();
+      trajopt::TrajArray t(static_cast<std::size_t>(N));
+      for (auto& row : t)
+      {
+        if (x)
+        {
+          row.assign(x, x + D);
+          x += D;
+        }
+      }
+      trajs.push_back(std::move(t));
+    }
+    // the slot map of problem 0 (no device call): counts, names, order
+    if (!probs[0]->lowerable())
+      throw std::runtime_error("thost_eval_json_batch: the batched kernels do not take this problem (" +
+                               trajopt::whyNotLowerable(*probs[0]) +
+                               "): evaluate it on the host loop (Cost::value / Constraint::violation)");
+    int nc = 0, nv = 0;
+    const std::vector<thip_term_slot> table = trajopt::termSlotTable(probs[0]->desc(), nc, nv);
+    const trajopt::TermSlotMap map = trajopt::termSlotMap(*probs[0], table, nc, nv);
+    if (n_costs)
+      *n_costs = nc;
+    if (n_cnts)
+      *n_cnts = nv;
+    if (slot_map)
+    {
+      std::copy(map.cost_pos.begin(), map.cost_pos.end(), slot_map);
+      std::copy(map.cnt_pos.begin(), map.cnt_pos.end(), slot_map + nc);
+    }
+    if (names)
+    {
+      std::string all;
+      for (const auto& n : map.cost_names)
+        all += n + "\n";
+      for (const auto& n : map.cnt_names)
+        all += n + "\n";
+      if (static_cast<int>(all.size()) + 1 > names_len)
+        throw std::runtime_error("thost_eval_json_batch: names need " + std::to_string(all.size() + 1) + " bytes");
+      std::memcpy(names, all.c_str(), all.size() + 1);
+    }
+    if (route == THOST_EVAL_NAMES)
+    {
+      setErr(err, err_len, "");
+      return 0;
+    }
+    if ((nc > 0 && !cost_vals) || (nv > 0 && !cnt_viols))
+      throw std::runtime_error("thost_eval_json_batch: null cost_vals / cnt_viols");
+    if (route == THOST_EVAL_DEVICE)
+    {
+      trajopt::TermEvaluator ev(probs, device);
+      const auto res = ev.evaluate(trajs);
+      for (int b = 0; b < batch; ++b)
+      {
+        const auto& r = res[static_cast<std::size_t>(b)];
+        std::copy(r.cost_vals.begin(), r.cost_vals.end(), cost_vals + static_cast<std::size_t>(b) * nc);
+        std::copy(r.cnt_viols.begin(), r.cnt_viols.end(), cnt_viols + static_cast<std::size_t>(b) * nv);
+      }
+    }
+    else
+    {
+      for (int b = 0; b < batch; ++b)
+      {
+        auto& p = *probs[static_cast<std::size_t>(b)];
+        const trajopt::DblVec xb = trajopt::trajToDblVec(trajs[static_cast<std::size_t>(b)]);
+        p.prefetch(xb);
+        const auto& costs = p.getCosts();
+        const auto cnts = p.getConstraints();
+        if (static_cast<int>(costs.size()) != nc || static_cast<int>(cnts.size()) != nv)
+          throw std::runtime_error("thost_eval_json_batch: problem " + std::to_string(b) +
+                                   " does not share problem 0's terms");
+        for (int i = 0; i < nc; ++i)
+          cost_vals[static_cast<std::size_t>(b) * nc + i] = costs[static_cast<std::size_t>(i)]->value(xb);
+        for (int i = 0; i < nv; ++i)
+          cnt_viols[static_cast<std::size_t>(b) * nv + i] = cnts[static_cast<std::size_t>(i)]->violation(xb);
+      }
+    }
+    setErr(err, err_len, "");
+    return 0;
+  }
+  catch (const std::exception& e)
+  {
+    setErr(err, err_len, e.what());
+    return -1;
+  }
+}
+
 int thost_solve_json(const char* json_text, const double* scene, int n_prims, int device, double* x,
                      thip_result* result, int* native, char* err, int err_len)
 {
@@ -210,6 +316,56 @@ void toResult(const sco::OptResults& r, thip_result& o)
   o.flags = r.flags;
 }
 }  // namespace
+
+int thost_solve_json_batch_terms(const char* const* json_texts, int batch, const double* scenes, int n_prims,
+                                 int device, int drop_in, double* x, thip_result* results, int* sizes,
+                                 double* cost_vals, int cap_costs, double* cnt_viols, int cap_cnts, char* err,
+                                 int err_len)
+{
+  try
+  {
+    if (!json_texts || batch <= 0 || !x || !sizes || cap_costs < 0 || cap_cnts < 0 || (cap_costs > 0 && !cost_vals) ||
+        (cap_cnts > 0 && !cnt_viols))
+      throw std::runtime_error("thost_solve_json_batch_terms: bad arguments");
+    std::vector<trajopt::TrajOptProb::Ptr> probs;
+    for (int b = 0; b < batch; ++b)
+      probs.push_back(construct(json_texts[b], scenes ? scenes + static_cast<std::size_t>(b) * n_prims * 16 : nullptr,
+                                n_prims));
+    std::vector<sco::OptResults> res;
+    if (drop_in)
+      for (const auto& p : probs)
+      {
+        trajopt::BasicTrustRegionSQP opt(p, device);
+        opt.initialize(trajopt::trajToDblVec(p->GetInitTraj()));
+        opt.optimize();
+        res.push_back(opt.results());
+      }
+    else
+      res = trajopt::BatchTrustRegionSQP(probs, device).optimize();
+    sizes[0] = static_cast<int>(res[0].cost_vals.size());
+    sizes[1] = static_cast<int>(res[0].cnt_viols.size());
+    for (std::size_t b = 0; b < res.size(); ++b)
+    {
+      const auto& r = res[b];
+      if (static_cast<int>(r.cost_vals.size()) > cap_costs || static_cast<int>(r.cnt_viols.size()) > cap_cnts)
+        throw std::runtime_error("thost_solve_json_batch_terms: problem " + std::to_string(b) + " has " +
+                                 std::to_string(r.cost_vals.size()) + " cost values and " +
+                                 std::to_string(r.cnt_viols.size()) + " violations");
+      std::copy(r.x.begin(), r.x.end(), x + b * r.x.size());
+      std::copy(r.cost_vals.begin(), r.cost_vals.end(), cost_vals + b * static_cast<std::size_t>(cap_costs));
+      std::copy(r.cnt_viols.begin(), r.cnt_viols.end(), cnt_viols + b * static_cast<std::size_t>(cap_cnts));
+      if (results)
+        toResult(r, results[b]);
+    }
+    setErr(err, err_len, "");
+    return 0;
+  }
+  catch (const std::exception& e)
+  {
+    setErr(err, err_len, e.what());
+    return -1;
+  }
+}
 
 int thost_solve_json_stream(const char* const* json_texts, int n_batches, int batch, const double* scenes, int n_prims,
                             const int* devices, int n_devices, int inflight, double* x, thip_result* results, char* err,

@@ -211,14 +211,14 @@ trajopt::JointDiffSpec diffSpec(trajopt::TrajOptProb& prob, int order, const tra
 
 // the host cost / constraint object of a joint-difference term (trajectory_costs.hpp)
 void addJointDiffObjects(trajopt::TrajOptProb& prob, const trajopt::JointDiffSpec& s, bool is_cost, bool zero_tols,
-                         const std::string& name, bool lowered)
+                         const std::string& name, bool lowered, int kind = -1, int index = -1)
 {
   if (is_cost)
   {
     sco::Cost::Ptr c = zero_tols ? sco::Cost::Ptr(std::make_shared<trajopt::JointDiffEqCost>(s, name))
                                  : sco::Cost::Ptr(std::make_shared<trajopt::JointDiffIneqCost>(s, name));
     if (lowered)
-      prob.addLoweredCost(c);
+      prob.addLoweredCost(c, kind, index);
     else
       prob.addCost(c);
   }
@@ -228,7 +228,7 @@ void addJointDiffObjects(trajopt::TrajOptProb& prob, const trajopt::JointDiffSpe
                                  ? sco::Constraint::Ptr(std::make_shared<trajopt::JointDiffEqConstraint>(s, name))
                                  : sco::Constraint::Ptr(std::make_shared<trajopt::JointDiffIneqConstraint>(s, name));
     if (lowered)
-      prob.addLoweredConstraint(c);
+      prob.addLoweredConstraint(c, kind, index);
     else
       prob.addConstraint(c);
   }
@@ -265,7 +265,7 @@ void addJointDiffTerm(trajopt::TrajOptProb& prob, int order, bool is_cost, const
   // only on the generic path
   const bool zero_tols = allZero(upper) && allZero(lower);
   addJointDiffObjects(prob, diffSpec(prob, order, coeffs, targets, upper, lower, first, last), is_cost, zero_tols,
-                      name, order == 2 && is_cost && zero_tols);
+                      name, order == 2 && is_cost && zero_tols, THIP_TERM_JDT, k);
 }
 
 sco::ModelConfig::ConstPtr modelConfig(const trajopt::ProblemConstructionInfo& pci)
@@ -579,7 +579,7 @@ void JointPosTermInfo::hatch(TrajOptProb& prob)
     prob.jpos_targets.push_back(targets[j]);
   }
   addJointDiffObjects(prob, diffSpec(prob, 0, coeffs, targets, upper_tols, lower_tols, first_step, last_step),
-                      !d.jpos_is_cnt[k], allZero(upper_tols) && allZero(lower_tols), name, true);
+                      !d.jpos_is_cnt[k], allZero(upper_tols) && allZero(lower_tols), name, true, THIP_TERM_JPOS, k);
 }
 
 // ------------------------------------------------------------ JointVel
@@ -680,7 +680,7 @@ void JointVelTermInfo::hatch(TrajOptProb& prob)
       d.jvx_upper_tols[x][j] = upper_tols[j];
       d.jvx_lower_tols[x][j] = lower_tols[j];
     }
-    addJointDiffObjects(prob, spec, is_cost, false, name, true);
+    addJointDiffObjects(prob, spec, is_cost, false, name, true, THIP_TERM_JVX, x);
     return;
   }
   if (d.jv_enabled)
@@ -700,7 +700,7 @@ void JointVelTermInfo::hatch(TrajOptProb& prob)
     d.jv_upper_tols[j] = upper_tols[j];  // nonzero: JointVelIneqCost
     d.jv_lower_tols[j] = lower_tols[j];
   }
-  addJointDiffObjects(prob, spec, true, zero_tols, name, true);
+  addJointDiffObjects(prob, spec, true, zero_tols, name, true, THIP_TERM_JOINT_VEL, 0);
 }
 
 // ------------------------------------------------------------ JointAcc / JointJerk
@@ -955,9 +955,10 @@ void CartPoseTermInfo::hatch(TrajOptProb& prob)
   auto dfdx = std::make_shared<CartPoseDeviceJac>(prob.deviceTerms(), k, indices);
   const sco::VarVector vars = prob.GetVarRow(timestep, 0, prob.GetNumDOF());
   if (d.cart_is_cnt[k])
-    prob.addLoweredConstraint(std::make_shared<DeviceCartPoseConstraint>(f, dfdx, vars, coeffs, sco::EQ, name));
+    prob.addLoweredConstraint(std::make_shared<DeviceCartPoseConstraint>(f, dfdx, vars, coeffs, sco::EQ, name),
+                              THIP_TERM_CART, k);
   else
-    prob.addLoweredCost(std::make_shared<DeviceCartPoseCost>(f, dfdx, vars, coeffs, sco::ABS, name));
+    prob.addLoweredCost(std::make_shared<DeviceCartPoseCost>(f, dfdx, vars, coeffs, sco::ABS, name), THIP_TERM_CART, k);
 }
 
 // ------------------------------------------------------------ Collision
@@ -1162,7 +1163,7 @@ void CollisionTermInfo::hatch(TrajOptProb& prob)
       if (extra)
         prob.addConstraint(c);
       else
-        prob.addLoweredConstraint(c);
+        prob.addLoweredConstraint(c, THIP_TERM_COLL, -1, i);
     }
     else
     {
@@ -1170,7 +1171,7 @@ void CollisionTermInfo::hatch(TrajOptProb& prob)
       if (extra)
         prob.addCost(c);
       else
-        prob.addLoweredCost(c);
+        prob.addLoweredCost(c, THIP_TERM_COLL, -1, i);
     }
   };
   auto fixedStep = [&](int i) { return std::find(fixed_steps.begin(), fixed_steps.end(), i) != fixed_steps.end(); };
@@ -1437,15 +1438,17 @@ TrajOptProb::TrajOptProb(int n_steps, const ProblemConstructionInfo& pci)
       joint_vars_.data.push_back(traj_vars_(i, j));
 }
 
-void TrajOptProb::addLoweredCost(sco::Cost::Ptr c)
+void TrajOptProb::addLoweredCost(sco::Cost::Ptr c, int kind, int index, int unit)
 {
   lowered_.push_back(c.get());
+  lowered_records_.push_back({ c.get(), kind, index, unit, 0 });
   addCost(std::move(c));
 }
 
-void TrajOptProb::addLoweredConstraint(sco::Constraint::Ptr c)
+void TrajOptProb::addLoweredConstraint(sco::Constraint::Ptr c, int kind, int index, int unit)
 {
   lowered_.push_back(c.get());
+  lowered_records_.push_back({ c.get(), kind, index, unit, 1 });
   addConstraint(std::move(c));
 }
 

@@ -1,11 +1,13 @@
 // trajopt_batch: solve JSON problems (the reference's TrajOptRequest format)
 // as one batch on one MI355X through the C++ front door.
-//   trajopt_batch [--device D] [--repeat R] [--check] problem.json [problem.json ...]
+//   trajopt_batch [--device D] [--repeat R] [--check] [--terms] problem.json [problem.json ...]
 // Every file is one problem (all must share one structure); --repeat R
 // replicates the list R times.  Prints one line per problem.  --check: after
 // the solve, each problem's checkTrajectory verdict (a CONTINUOUS check with
 // margin 0, as planning_unit.cpp runs it) and clearance, from the trajectories
-// on the device.
+// on the device.  --terms: one line per problem and term with its name and its
+// cost value or constraint violation at the returned trajectory
+// (OptResults::cost_vals / cnt_viols).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,7 +20,7 @@
 int main(int argc, char** argv)
 {
   int device = 0, repeat = 1;
-  bool do_check = false;
+  bool do_check = false, do_terms = false;
   std::vector<std::string> files;
   for (int i = 1; i < argc; ++i)
   {
@@ -28,12 +30,14 @@ int main(int argc, char** argv)
       repeat = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--check"))
       do_check = true;
+    else if (!std::strcmp(argv[i], "--terms"))
+      do_terms = true;
     else
       files.emplace_back(argv[i]);
   }
   if (files.empty() || repeat < 1)
   {
-    std::fprintf(stderr, "usage: %s [--device D] [--repeat R] [--check] problem.json [...]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [--device D] [--repeat R] [--check] [--terms] problem.json [...]\n", argv[0]);
     return 2;
   }
   try
@@ -50,6 +54,16 @@ int main(int argc, char** argv)
                   sco::toString(res[b].status).c_str(), res[b].n_sqp_iters, res[b].n_qp_solves, res[b].total_cost,
                   res[b].max_cnt_viol);
     std::printf("kernel %.3f ms for %zu problems\n", opt.lastKernelMs(), res.size());
+    if (do_terms)
+      for (std::size_t b = 0; b < res.size(); ++b)
+      {
+        const auto& costs = probs[b]->getCosts();
+        const auto cnts = probs[b]->getConstraints();
+        for (std::size_t i = 0; i < res[b].cost_vals.size() && i < costs.size(); ++i)
+          std::printf("problem %zu: cost %s %.12g\n", b, costs[i]->name().c_str(), res[b].cost_vals[i]);
+        for (std::size_t i = 0; i < res[b].cnt_viols.size() && i < cnts.size(); ++i)
+          std::printf("problem %zu: constraint %s %.12g\n", b, cnts[i]->name().c_str(), res[b].cnt_viols[i]);
+      }
     if (do_check)
     {
       // a host-loop batch keeps its trajectories on the host

@@ -289,6 +289,22 @@ class CheckResult(C.Structure):
     ]
 
 
+TERM_JOINT_VEL, TERM_JVX, TERM_JPOS, TERM_JDT, TERM_CART, TERM_COLL = range(6)  # thip_term_slot.kind (THIP_TERM_*)
+TERM_KIND_NAMES = ("joint_vel", "jvx", "jpos", "jdt", "cart", "coll")
+# workspace arrays of layout.hpp's DArr / IArr that thip_debug_layout + thip_debug_workspace expose to tests
+WS_A_COST, WS_A_VIOL, WS_I_PCNT = 6, 7, 10
+
+
+class TermSlot(C.Structure):
+    """thip_term_slot: what one cost / constraint slot of thip_terms_run holds."""
+    _fields_ = [
+        ("kind", C.c_int),
+        ("index", C.c_int),
+        ("unit", C.c_int),
+        ("is_cnt", C.c_int),
+    ]
+
+
 def default_check_config() -> CheckConfig:
     """thip_default_check_config: one cast per step pair (CONTINUOUS), margin 0, every step."""
     return CheckConfig(CHECK_LVS_CONTINUOUS, float("inf"), 0.0, 0, -1)
@@ -436,6 +452,38 @@ def _declare(lib):
     lib.thip_check_destroy.restype = None
     lib.thip_check_last_error.argtypes = [vp]
     lib.thip_check_last_error.restype = C.c_char_p
+    lib.thip_sizeof_term_slot.argtypes = []
+    lib.thip_sizeof_term_slot.restype = C.c_int
+    lib.thip_terms_create.argtypes = [C.c_int, P(ProblemDesc), C.c_int, P(vp)]
+    lib.thip_terms_create.restype = C.c_int
+    lib.thip_terms_slot_table.argtypes = [P(ProblemDesc), P(TermSlot), C.c_int, P(C.c_int), P(C.c_int)]
+    lib.thip_terms_slot_table.restype = C.c_int
+    lib.thip_terms_counts.argtypes = [vp, P(C.c_int), P(C.c_int)]
+    lib.thip_terms_counts.restype = C.c_int
+    lib.thip_terms_slots.argtypes = [vp, P(TermSlot)]
+    lib.thip_terms_slots.restype = C.c_int
+    lib.thip_terms_upload.argtypes = [vp, dp, dp]
+    lib.thip_terms_upload.restype = C.c_int
+    lib.thip_terms_upload_device.argtypes = [vp, vp, vp]
+    lib.thip_terms_upload_device.restype = C.c_int
+    lib.thip_terms_upload_joint_targets.argtypes = [vp, dp]
+    lib.thip_terms_upload_joint_targets.restype = C.c_int
+    lib.thip_terms_upload_joint_targets_device.argtypes = [vp, vp]
+    lib.thip_terms_upload_joint_targets_device.restype = C.c_int
+    lib.thip_terms_run.argtypes = [vp, dp, dp, dp]
+    lib.thip_terms_run.restype = C.c_int
+    lib.thip_terms_run_device.argtypes = [vp, vp, dp, dp]
+    lib.thip_terms_run_device.restype = C.c_int
+    lib.thip_terms_last_ms.argtypes = [vp]
+    lib.thip_terms_last_ms.restype = C.c_double
+    lib.thip_terms_destroy.argtypes = [vp]
+    lib.thip_terms_destroy.restype = None
+    lib.thip_terms_last_error.argtypes = [vp]
+    lib.thip_terms_last_error.restype = C.c_char_p
+    lib.thip_debug_layout.argtypes = [vp, P(C.c_longlong), P(C.c_longlong), P(C.c_longlong)]
+    lib.thip_debug_layout.restype = C.c_int
+    lib.thip_debug_workspace.argtypes = [vp, dp, P(C.c_int)]
+    lib.thip_debug_workspace.restype = C.c_int
     lib.thip_sizeof_desc.argtypes = []
     lib.thip_sizeof_desc.restype = C.c_int
     lib.thip_sizeof_result.argtypes = []
@@ -466,6 +514,8 @@ def load_hip():
         if (_hip.thip_sizeof_check_config() != C.sizeof(CheckConfig)
                 or _hip.thip_sizeof_check_result() != C.sizeof(CheckResult)):
             raise RuntimeError("thip_check_config / thip_check_result layout mismatch between Python and the HIP library")
+        if _hip.thip_sizeof_term_slot() != C.sizeof(TermSlot):
+            raise RuntimeError("thip_term_slot layout mismatch between Python and the HIP library")
     return _hip
 
 

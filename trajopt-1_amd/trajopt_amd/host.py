@@ -67,6 +67,14 @@ def load_host():
                                              C.POINTER(abi.CheckConfig), C.c_int, C.POINTER(abi.CheckResult),
                                              C.c_char_p, C.c_int]
         L.thost_check_json_batch.restype = C.c_int
+        L.thost_eval_json_batch.argtypes = [C.POINTER(C.c_char_p), C.c_int, dp, C.c_int, dp, C.c_int, C.c_int,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp, C.c_char_p, C.c_int,
+                                            C.POINTER(C.c_int), C.c_char_p, C.c_int]
+        L.thost_eval_json_batch.restype = C.c_int
+        L.thost_solve_json_batch_terms.argtypes = [C.POINTER(C.c_char_p), C.c_int, dp, C.c_int, C.c_int, C.c_int, dp,
+                                                   C.POINTER(abi.Result), C.POINTER(C.c_int), dp, C.c_int, dp,
+                                                   C.c_int, C.c_char_p, C.c_int]
+        L.thost_solve_json_batch_terms.restype = C.c_int
         L.thost_solve_json.argtypes = [C.c_char_p, dp, C.c_int, C.c_int, dp, C.POINTER(abi.Result),
                                        C.POINTER(C.c_int), C.c_char_p, C.c_int]
         L.thost_solve_json.restype = C.c_int
@@ -146,6 +154,69 @@ def check_json_batch(texts, scenes, trajectories, config=None, device=0):
     if L.thost_check_json_batch(arr, B, _dp(sc), n_prims, _dp(x), C.byref(cfg), device, res, err, 4096) != 0:
         raise HostError(err.value.decode())
     return list(res)
+
+
+EVAL_DEVICE, EVAL_OBJECTS, EVAL_NAMES = 0, 1, 2  # THOST_EVAL_*
+
+
+def eval_json_batch(texts, scenes, trajectories, route=EVAL_DEVICE, device=0):
+    """trajopt::TermEvaluator for lowerable JSON problems (thost_eval_json_batch): the
+    value of every cost and the violation of every constraint of each problem at its
+    trajectory (trajectories [B, N, D]) in prob->getCosts() / getConstraints() order
+    -> dict(cost_names, cnt_names, cost_vals [B, n_costs], cnt_viols [B, n_cnts],
+    slot_map).  route EVAL_DEVICE: the batched term-value kernels; EVAL_OBJECTS: the
+    host term objects (Cost::value / Constraint::violation); EVAL_NAMES: names, counts
+    and the kernel-slot -> term-position map only (no device call, trajectories may be
+    None)."""
+    L = load_host()
+    B = len(texts)
+    sc = None if scenes is None else np.ascontiguousarray(scenes, dtype=np.float64)
+    n_prims = 0 if sc is None else sc.shape[1]
+    arr = (C.c_char_p * B)(*[t.encode() for t in texts])
+    err = C.create_string_buffer(4096)
+    names = C.create_string_buffer(1 << 16)
+    nc, nv = C.c_int(0), C.c_int(0)
+    smap = (C.c_int * 1024)()
+    if L.thost_eval_json_batch(arr, B, _dp(sc), n_prims, None, EVAL_NAMES, device, C.byref(nc), C.byref(nv), None, None,
+                               names, len(names), smap, err, 4096) != 0:
+        raise HostError(err.value.decode())
+    all_names = names.value.decode().split("\n")[:-1]
+    out = {"cost_names": all_names[: nc.value], "cnt_names": all_names[nc.value:],
+           "slot_map": list(smap)[: nc.value + nv.value], "cost_vals": None, "cnt_viols": None}
+    if route == EVAL_NAMES:
+        return out
+    x = np.ascontiguousarray(trajectories, dtype=np.float64)
+    if x.ndim != 3 or x.shape[0] != B:
+        raise HostError(f"eval_json_batch: trajectories of shape {x.shape} for {B} problems")
+    cv, vv = np.zeros((B, nc.value)), np.zeros((B, nv.value))
+    if L.thost_eval_json_batch(arr, B, _dp(sc), n_prims, _dp(x), route, device, None, None, _dp(cv), _dp(vv), None, 0,
+                               None, err, 4096) != 0:
+        raise HostError(err.value.decode())
+    out["cost_vals"], out["cnt_viols"] = cv, vv
+    return out
+
+
+def solve_json_batch_terms(texts, scenes=None, device=0, drop_in=False):
+    """solve_json_batch with OptResults::cost_vals / cnt_viols (thost_solve_json_batch_terms):
+    through trajopt::BatchTrustRegionSQP, or (drop_in) problem by problem through the
+    trajopt::BasicTrustRegionSQP drop-in -> (x, results, cost_vals [B, n], cnt_viols [B, m])."""
+    L = load_host()
+    B = len(texts)
+    desc, _, _, _ = lower_json(texts[0], None if scenes is None else scenes[0])
+    N, D = desc.n_steps, desc.chain.n_dof + (1 if desc.use_time else 0)
+    sc = None if scenes is None else np.ascontiguousarray(scenes, dtype=np.float64)
+    n_prims = 0 if sc is None else sc.shape[1]
+    arr = (C.c_char_p * B)(*[t.encode() for t in texts])
+    x = np.zeros((B, N, D))
+    res = (abi.Result * B)()
+    cap = 512
+    cv, vv = np.zeros((B, cap)), np.zeros((B, cap))
+    sizes = (C.c_int * 2)()
+    err = C.create_string_buffer(4096)
+    if L.thost_solve_json_batch_terms(arr, B, _dp(sc), n_prims, device, 1 if drop_in else 0, _dp(x), res, sizes,
+                                      _dp(cv), cap, _dp(vv), cap, err, 4096) != 0:
+        raise HostError(err.value.decode())
+    return x, list(res), cv[:, : sizes[0]].copy(), vv[:, : sizes[1]].copy()
 
 
 def last_batch_qp_stats():

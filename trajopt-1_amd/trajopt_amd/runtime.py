@@ -123,6 +123,35 @@ class BatchTrustRegionSQP:
         finally:
             chk.close()
 
+    def term_values(self):
+        """The value of every cost and the violation of every constraint at the last
+        solve's trajectories where they lie on the device (thip_device_x): costs
+        [B, n_costs], viols [B, n_cnts] (OptResults::cost_vals / cnt_viols in slot
+        order; TermValues.slots names the slots).  Explicit: no other method
+        evaluates terms."""
+        self.sync()
+        tv = TermValues(self.wl, device=self._device)
+        try:
+            return tv.run_device(self.lib.thip_device_x(self.ctx))
+        finally:
+            tv.close()
+
+    def debug_values(self):
+        """Diagnostic: the solver's own A_COST / A_VIOL [B, n_costs] / [B, n_cnts] and the
+        contact counts I_PCNT [B, N] read from the workspace (thip_debug_layout +
+        thip_debug_workspace).  They belong to the returned trajectories only under
+        abi.DEBUG_STATIC_DISPATCH, where every problem keeps its workspace."""
+        doff = (C.c_longlong * 256)()
+        ioff = (C.c_longlong * 256)()
+        dims = (C.c_longlong * 12)()
+        self._check(self.lib.thip_debug_layout(self.ctx, doff, ioff, dims), "thip_debug_layout")
+        dstride, istride = int(dims[8]), int(dims[9])
+        dws = np.zeros((self.batch, dstride))
+        iws = np.zeros((self.batch, istride), dtype=np.int32)
+        self._check(self.lib.thip_debug_workspace(self.ctx, _dp(dws), iws.ctypes.data_as(C.POINTER(C.c_int))),
+                    "thip_debug_workspace")
+        return dws, iws, list(doff), list(ioff)
+
     def enable_trace(self, capacity=512):
         self._trace_cap = capacity
         self._check(self.lib.thip_debug_trace(self.ctx, capacity), "thip_debug_trace")
@@ -218,6 +247,80 @@ class TermEvaluator:
         if self.ev:
             self.lib.thip_eval_destroy(self.ev)
             self.ev = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TermValues:
+    """thip_terms_*: the value of every cost and the violation of every constraint
+    of every problem of a workload at any trajectories (OptResults::cost_vals /
+    cnt_viols of the reference), in the fused kernel's slot order.  Takes the
+    descriptors thip_create takes (contact test ALL, FIRST or CLOSEST); anything
+    else raises."""
+
+    def __init__(self, workload, device: int = 0):
+        self.lib = abi.load_hip()
+        self.wl = workload
+        self.batch = workload.batch
+        self.t = C.c_void_p()
+        rc = self.lib.thip_terms_create(device, C.byref(workload.desc), self.batch, C.byref(self.t))
+        if rc != 0:
+            raise HipError(f"thip_terms_create: {self.lib.thip_terms_last_error(None).decode()}")
+        nc, nv = C.c_int(), C.c_int()
+        self._check(self.lib.thip_terms_counts(self.t, C.byref(nc), C.byref(nv)), "thip_terms_counts")
+        self.n_costs, self.n_cnts = nc.value, nv.value
+        tab = (abi.TermSlot * max(self.n_costs + self.n_cnts, 1))()
+        self._check(self.lib.thip_terms_slots(self.t, tab), "thip_terms_slots")
+        self.slots = list(tab)[: self.n_costs + self.n_cnts]
+        self._tgt = np.ascontiguousarray(workload.targets, dtype=np.float64) if workload.targets.size else None
+        self._scene = np.ascontiguousarray(workload.scene, dtype=np.float64) if workload.scene.size else None
+        self._check(self.lib.thip_terms_upload(self.t, None if self._tgt is None else _dp(self._tgt),
+                                               None if self._scene is None else _dp(self._scene)), "thip_terms_upload")
+        jt = getattr(workload, "jpos_targets", None)
+        if jt is not None:
+            self._jpt = np.ascontiguousarray(jt, dtype=np.float64)
+            self._check(self.lib.thip_terms_upload_joint_targets(self.t, _dp(self._jpt)),
+                        "thip_terms_upload_joint_targets")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise HipError(f"{what}: {self.lib.thip_terms_last_error(self.t).decode()}")
+
+    def slot_names(self):
+        """One readable name per slot, costs first: e.g. 'cost:cart[3]', 'cnt:coll[2]@t=2'."""
+        return [("cnt:" if s.is_cnt else "cost:") + f"{abi.TERM_KIND_NAMES[s.kind]}[{s.index}]"
+                + (f"@t={s.unit}" if s.unit >= 0 else "") for s in self.slots]
+
+    def _out(self):
+        return np.zeros((self.batch, self.n_costs)), np.zeros((self.batch, self.n_cnts))
+
+    def run(self, x):
+        """x [B, N, D] (host) -> costs [B, n_costs], viols [B, n_cnts]."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != self.batch * self.wl.n_steps * self.wl.n_dof:
+            raise HipError(f"TermValues.run: x has {x.size} values, not [batch][n_steps][n_dof]")
+        costs, viols = self._out()
+        self._check(self.lib.thip_terms_run(self.t, _dp(x), _dp(costs), _dp(viols)), "thip_terms_run")
+        return costs, viols
+
+    def run_device(self, d_x):
+        """As run() on trajectories already on the device (an address, e.g. thip_device_x)."""
+        costs, viols = self._out()
+        self._check(self.lib.thip_terms_run_device(self.t, C.c_void_p(d_x), _dp(costs), _dp(viols)),
+                    "thip_terms_run_device")
+        return costs, viols
+
+    def kernel_ms(self) -> float:
+        return float(self.lib.thip_terms_last_ms(self.t))
+
+    def close(self):
+        if self.t:
+            self.lib.thip_terms_destroy(self.t)
+            self.t = C.c_void_p()
 
     def __del__(self):
         try:
