@@ -592,6 +592,10 @@ int thip_debug_layout(thip_ctx* ctx, long long* doff, long long* ioff, long long
 #define THIP_DEBUG_SEG_RETURN 128     /* the ADMM segment returns to qp_solve() at every termination check and
                                          check_termination ignores the segment's third infeasibility tests, as
                                          before round 8 (bitwise the same results) */
+#define THIP_DEBUG_SETUP_REF 256      /* the QP set-up gathers the Ruiz column norms with the serial per-column
+                                         loops over the hinge and CartPose rows and factors the narrow (D <= 8)
+                                         diagonal blocks through LDS, as before round 9 (bitwise the same
+                                         results) */
 int thip_debug_set_path(int flags);
 int thip_debug_workspace(thip_ctx* ctx, double* dws, int* iws);
 /* The solve layout a context chose (diagnostic): out[0] block-solve branches

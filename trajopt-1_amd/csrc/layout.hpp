@@ -259,6 +259,10 @@ struct Layout
   // step_rows indirection (max_step_rows: the most rows of one waypoint)
   int rows_contig;
   int max_step_rows;
+  // diagnostic (THIP_DEBUG_SETUP_REF): build_and_scale gathers the Ruiz column
+  // norms with the serial per-column loops, and factor() / twisted_factor_half
+  // run the block Cholesky through LDS with one lane per row (read there only)
+  int setup_ref;
 };
 
 // the solve-layout index of column col (t, j): block b * N + t, row j - b sD

@@ -1889,6 +1889,80 @@ __device__ __forceinline__ int row_kind(const Layout& L, int r, int& idx)
   return RK_HINGE;
 }
 
+// ---- Ruiz scaling: gathering the hinge rows' maxima -----------------------
+// The column norms are maxima of absolute values: exact and independent of the
+// order, so any split gives the same bits.  A column's hinge share used to be
+// a serial walk over every hinge row of its two step pairs (hundreds of
+// dependent loads on a few columns while the workgroup waits at the barrier).
+// Instead the passes that write A_HC anyway (the unscaled fill, the
+// scale-apply pass) fold |HC[e]| into a per-column maximum for the next
+// column-norm pass: an integer max over the bit patterns, which orders
+// non-negative doubles as fmax does.  The maxima live in A_HPART (idle outside
+// the solve; >= (N + 1) part_w >= nx doubles whenever the QP has hinge rows).
+__device__ __forceinline__ bool lds_resident(const Ctx& c, const double* p);
+typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+typedef __attribute__((address_space(1))) unsigned long long gbl_u64;
+__device__ __forceinline__ void absmax_fold(lds_f64* p, double v)
+{
+  const double a = fabs(v);
+  if (a == a)  // fmax passes over a NaN operand
+    __hip_atomic_fetch_max((lds_u64*)p, (unsigned long long)__double_as_longlong(a), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void absmax_fold(gbl_f64* p, double v)
+{
+  const double a = fabs(v);
+  if (a == a)
+    __hip_atomic_fetch_max((gbl_u64*)p, (unsigned long long)__double_as_longlong(a), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// f(typed pointer) for an array of the residency plan: LDS or the HBM workspace
+template <typename F>
+__device__ __forceinline__ void with_space(const Ctx& c, double* p, F&& f)
+{
+  if (lds_resident(c, p))
+    f(lds(p));
+  else
+    f(gbl(p));
+}
+// max(v, |H[k]|, k < n): 16 loads issued together (a repeated entry is neutral)
+template <typename HP>
+__device__ __forceinline__ double row_absmax(HP H, int n, double v)
+{
+  for (int k0 = 0; k0 < n; k0 += 16)
+  {
+    double g[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      g[i] = H[min(k0 + i, n - 1)];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      v = fmax(v, fabs(g[i]));
+  }
+  return v;
+}
+// max(v, |GS[SR[p] * D + j]|, p0 <= p < p1), the CartPose rows of a waypoint:
+// the index loads first, then the data loads, then the max
+__device__ __forceinline__ double step_rows_absmax(const int* SR, const double* GS, int p0, int p1, int D, int j,
+                                                   double v)
+{
+  for (int p = p0; p < p1; p += 8)
+  {
+    int a[8];
+    double g[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      a[i] = SR[min(p + i, p1 - 1)];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      g[i] = GS[a[i] * D + j];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      v = fmax(v, fabs(g[i]));
+  }
+  return v;
+}
+
 __device__ void build_and_scale(Ctx& c)
 {
   PROF(7);
@@ -2001,6 +2075,9 @@ __device__ void build_and_scale(Ctx& c)
   // viol = margin - (k + a.x): row coefficients -a (x_t, x_t+1) and -1 (h),
   // objective coeff * h (modeling.cpp:19-27)
   const int nh = c.s->n_h;
+  // diagnostic (THIP_DEBUG_SETUP_REF): the serial column-norm loops
+  const bool setup_ref = L.setup_ref != 0;
+  double* const CM = c.a(A_HPART);  // hinge share of the column maxima (nh > 0)
   {
     const double* HC0 = c.a(A_HC0);
     double *HC = c.a(A_HC), *HW = c.a(A_HW);
@@ -2009,11 +2086,29 @@ __device__ void build_and_scale(Ctx& c)
     // static rows (kind 1) are stored as the affine expression itself: addHinge(aff, 1) for
     // costs, cntsToCosts' addHinge(aff, mu) for constraints
     const int *HTq = c.ia(I_HT), *HKDq = c.ia(I_HKIND), *HSLq = c.ia(I_HSLOT);
-    FOR(e, nh * 2 * D)
+    if (nh > 0 && !setup_ref)
     {
-      const int h = e / (2 * D);
-      HC[e] = HKDq[h] ? HC0[e] : (L.coll_cnt ? (-HC0[e]) * row_pair_mc(c, h).y : -HC0[e]);
+      // the same fill, folding |HC[e]| into the column maxima of the first Ruiz iteration
+      FOR(col, nx) CM[col] = 0.0;
+      BSYNC();
+      with_space(c, HC, [&](auto HCt) {
+        with_space(c, CM, [&](auto CMt) {
+          FOR(e, nh * 2 * D)
+          {
+            const int h = e / (2 * D), k = e % (2 * D);
+            const double hv = HKDq[h] ? HC0[e] : (L.coll_cnt ? (-HC0[e]) * row_pair_mc(c, h).y : -HC0[e]);
+            HCt[e] = hv;
+            absmax_fold(CMt + ((HTq[h] + (k >= D ? 1 : 0)) * D + (k % D)), hv);
+          }
+        });
+      });
     }
+    else
+      FOR(e, nh * 2 * D)
+      {
+        const int h = e / (2 * D);
+        HC[e] = HKDq[h] ? HC0[e] : (L.coll_cnt ? (-HC0[e]) * row_pair_mc(c, h).y : -HC0[e]);
+      }
     FOR(h, nh)
     {
       HW[h] = -1.0;
@@ -2033,6 +2128,7 @@ __device__ void build_and_scale(Ctx& c)
   BSYNC();
   double* Dt = c.a(A_DG);
   double* Et = c.a(A_PRV);
+  const bool hc_lds = lds_resident(c, c.a(A_HC));
   for (int it = 0; it < os.scaling; ++it)
   {
     // column norms of [P; A]
@@ -2057,17 +2153,30 @@ __device__ void build_and_scale(Ctx& c)
         const int f = c.T.fixed_of_step[t];
         if (f >= 0)
           v = fmax(v, fabs(FS[f * D + j]));
-        for (int p = c.T.step_ptr[t]; p < c.T.step_ptr[t + 1]; ++p)
-          v = fmax(v, fabs(GS[c.T.step_rows[p] * D + j]));
-        if (nh > 0)
+        if (setup_ref)
         {
-          const double* HC = c.a(A_HC);
-          const int* HP = c.ia(I_HPTR);
-          for (int h = HP[t]; h < HP[t + 1]; ++h)
-            v = fmax(v, fabs(HC[h * 2 * D + j]));
-          if (t > 0)
-            for (int h = HP[t - 1]; h < HP[t]; ++h)
-              v = fmax(v, fabs(HC[h * 2 * D + D + j]));
+          for (int p = c.T.step_ptr[t]; p < c.T.step_ptr[t + 1]; ++p)
+            v = fmax(v, fabs(GS[c.T.step_rows[p] * D + j]));
+          if (nh > 0)
+          {
+            const double* HC = c.a(A_HC);
+            const int* HP = c.ia(I_HPTR);
+            for (int h = HP[t]; h < HP[t + 1]; ++h)
+              v = fmax(v, fabs(HC[h * 2 * D + j]));
+            if (t > 0)
+              for (int h = HP[t - 1]; h < HP[t]; ++h)
+                v = fmax(v, fabs(HC[h * 2 * D + D + j]));
+          }
+        }
+        else
+        {
+          v = step_rows_absmax(c.T.step_rows, GS, c.T.step_ptr[t], c.T.step_ptr[t + 1], D, j, v);
+          if (nh > 0)
+          {
+            // folded by the pass that wrote A_HC; cleared for the next one
+            v = fmax(v, CM[col]);
+            CM[col] = 0.0;
+          }
         }
         v = fmax(v, fabs(BS[col]));
       }
@@ -2102,8 +2211,13 @@ __device__ void build_and_scale(Ctx& c)
       {
         const double* HC = c.a(A_HC);
         v = 0;
-        for (int k = 0; k < 2 * D; ++k)
-          v = fmax(v, fabs(HC[idx * 2 * D + k]));
+        if (setup_ref)
+          for (int k = 0; k < 2 * D; ++k)
+            v = fmax(v, fabs(HC[idx * 2 * D + k]));
+        else if (hc_lds)
+          v = row_absmax(lds(HC) + idx * 2 * D, 2 * D, v);
+        else
+          v = row_absmax(gbl(HC) + idx * 2 * D, 2 * D, v);
         v = fmax(v, fabs(c.a(A_HW)[idx]));
       }
       Et[r] = 1.0 / sqrt(limit_scaling(v));
@@ -2143,11 +2257,30 @@ __device__ void build_and_scale(Ctx& c)
     {
       double *HC = c.a(A_HC), *HW = c.a(A_HW);
       const int* HT = c.ia(I_HT);
-      FOR(e, nh * 2 * D)
+      if (setup_ref)
+        FOR(e, nh * 2 * D)
+        {
+          const int h = e / (2 * D), k = e % (2 * D);
+          const int col = (HT[h] + (k >= D ? 1 : 0)) * D + (k % D);
+          HC[e] = (HC[e] * Et[L.m_base + 2 * h]) * Dt[col];
+        }
+      else
       {
-        const int h = e / (2 * D), k = e % (2 * D);
-        const int col = (HT[h] + (k >= D ? 1 : 0)) * D + (k % D);
-        HC[e] = (HC[e] * Et[L.m_base + 2 * h]) * Dt[col];
+        // the same pass, folding |HC[e]| into the next iteration's column maxima
+        const bool fold = it + 1 < os.scaling;
+        with_space(c, HC, [&](auto HCt) {
+          with_space(c, CM, [&](auto CMt) {
+            FOR(e, nh * 2 * D)
+            {
+              const int h = e / (2 * D), k = e % (2 * D);
+              const int col = (HT[h] + (k >= D ? 1 : 0)) * D + (k % D);
+              const double hv = (HCt[e] * Et[L.m_base + 2 * h]) * Dt[col];
+              HCt[e] = hv;
+              if (fold)
+                absmax_fold(CMt + col, hv);
+            }
+          });
+        });
       }
       FOR(h, nh) HW[h] = (HW[h] * Et[L.m_base + 2 * h]) * Dt[L.nc_base + h];
     }
@@ -2300,6 +2433,75 @@ __device__ __forceinline__ void chol_inv_block(double* S, double* Li, int D, int
     chol_inv_block_t<kOct>(S, Li, D, lane, bad);
 }
 
+// lane l's v in every lane (l a compile-time constant after unrolling)
+__device__ __forceinline__ double lane_bcast(double v, int l)
+{
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+  return __hiloint2double(hi, lo);
+}
+
+// chol_inv_block for D <= kOct in registers: lane i (mod 8) holds row i of S,
+// rows and columns >= D padded with the identity, the column loop unrolled over
+// 8.  Column j broadcasts row j of L (complete up to its diagonal) once: the
+// lanes below take their entry of column j from it, and lane c takes row j of
+// column c of the inverse from the same values, so the two divisions of a
+// column overlap.  No LDS traffic and no wave_sync between the columns.  The
+// arithmetic is chol_inv_block_t's, term for term: v -= a b in increasing k,
+// sqrt, v / L[j][j] as a division, the not-positive-definite rule (the padded
+// terms subtract exact zeros, the padded pivots are sqrt(1)).
+__device__ __forceinline__ void chol_inv_block_reg(double* Sp, double* Lip, int D, int lane, int& bad)
+{
+  const lds_f64* S = lds(Sp);
+  lds_f64* Li = lds(Lip);
+  const int row = lane & (kOct - 1);
+  double r[kOct], x[kOct];
+#pragma unroll
+  for (int k = 0; k < kOct; ++k)
+  {
+    const double s = S[min(row, D - 1) * D + min(k, D - 1)];
+    r[k] = (row < D && k < D) ? s : ((row == k) ? 1.0 : 0.0);
+  }
+  bool npd = false;
+#pragma unroll
+  for (int j = 0; j < kOct; ++j)
+  {
+    double lj[kOct];  // L[j][k], k < j
+#pragma unroll
+    for (int k = 0; k < j; ++k)
+      lj[k] = lane_bcast(r[k], j);
+    // lane j: the pivot before its root; lanes below: their entry of column j
+    double v = r[j];
+#pragma unroll
+    for (int k = 0; k < j; ++k)
+      v -= r[k] * lj[k];
+    double d = lane_bcast(v, j);
+    if (!(d > 0))
+    {
+      npd = true;
+      d = 1.0;
+    }
+    const double ljj = sqrt(d);
+    r[j] = (row == j) ? ljj : ((row > j) ? v / ljj : r[j]);
+    // row j of the inverse's column `row`
+    double w = (row == j) ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 0; k < j; ++k)
+      w -= lj[k] * x[k];
+    x[j] = (j < row) ? 0.0 : w / ljj;
+  }
+  if (npd && lane == 0)
+    bad = 1;
+  if (lane < D)
+  {
+#pragma unroll
+    for (int i = 0; i < kOct; ++i)
+      if (i < D)
+        Li[i * D + lane] = x[i];
+  }
+  wave_sync();
+}
+
 // v + sum_{h in [h0, h1)} W[h] * (HC[h][a] * HC[h][b]), in order, 8 rows per
 // chunk with every load of the chunk issued first (masked rows add 0)
 __device__ __forceinline__ double hinge_outer_sum(const double* HC, const double* W, int stride, int a, int b, int h0,
@@ -2338,6 +2540,8 @@ __device__ __noinline__ void twisted_factor_half(Ctx& c, Solver& sv, const doubl
   const int D = L.sD, N = L.sNb, DD = D * D, m = L.tw_mid, half = c.wave & 1, base = (c.wave >> 1) * N;
   const int len = (half == 0) ? m : (N - 1 - m);
   const bool use_cpl = L.hinge || L.nbr > 1 || L.grp > 1;
+  // diagnostic (THIP_DEBUG_SETUP_REF): the Cholesky through LDS, one lane per row
+  [[maybe_unused]] const bool setup_ref = L.setup_ref != 0;
   lds_f64* S = lds(Sp);
   lds_f64* Ls = lds(Lsp);
   for (int k = 0; k < len; ++k)
@@ -2367,7 +2571,15 @@ __device__ __noinline__ void twisted_factor_half(Ctx& c, Solver& sv, const doubl
       S[e] = v;
     }
     wave_sync();
-    chol_inv_block(Sp, LIp + t * DD, D, c.lane, bad);
+    if constexpr (DM == kOct)
+    {
+      if (setup_ref)
+        chol_inv_block_t<kOct>(Sp, LIp + t * DD, D, c.lane, bad);
+      else
+        chol_inv_block_reg(Sp, LIp + t * DD, D, c.lane, bad);
+    }
+    else
+      chol_inv_block(Sp, LIp + t * DD, D, c.lane, bad);
     const lds_f64* Li = lds(LIp) + t * DD;
     for (int e = c.lane; e < DD; e += 64)
     {
@@ -2453,7 +2665,7 @@ __device__ __forceinline__ bool seg_path(const Ctx& c)
 }
 
 // returns false if the reduced matrix is not positive definite
-__device__ bool factor(Ctx& c, Solver& sv, double sigK, bool polish, double delta)
+__device__ __noinline__ bool factor(Ctx& c, Solver& sv, double sigK, bool polish, double delta)
 {
   PROF(3);
   long long* pf = (c.tid == 0) ? c.s->prof : nullptr;
@@ -2687,7 +2899,10 @@ __device__ bool factor(Ctx& c, Solver& sv, double sigK, bool polish, double delt
       S[e] = v;
     }
     wave_sync();
-    chol_inv_block(S, LI + mb * sDD, sD, c.lane, bad);
+    if (sD <= kOct && !L.setup_ref)
+      chol_inv_block_reg(S, LI + mb * sDD, sD, c.lane, bad);
+    else
+      chol_inv_block(S, LI + mb * sDD, sD, c.lane, bad);
     const double* Li = LI + mb * sDD;
     for (int e = c.lane; e < sDD; e += 64)
     {
@@ -3276,7 +3491,7 @@ __device__ __forceinline__ double chunk_sum_add(const double* PART, int pw, int 
 // column is summed per chunk of kHChunk rows of one step pair (even and odd
 // rows apart) and the chunk sums added in order: the association of
 // admm_segment's row-parallel gather, so that both paths give identical iterates.
-__device__ void reduced_solve(Ctx& c, Solver& sv, bool polish, double delta, const double* eta, double* out)
+__device__ __noinline__ void reduced_solve(Ctx& c, Solver& sv, bool polish, double delta, const double* eta, double* out)
 {
   long long* pf = (c.tid == 0) ? c.s->prof : nullptr;
   long long tq = pf ? clock64() : 0;
@@ -5524,7 +5739,7 @@ __device__ double rho_estimate(Ctx& c, const Norms& nm)
 }
 
 // polish: returns nothing; updates x/z/y buffers on success
-__device__ void polish(Ctx& c, Solver& sv, Norms& nm)
+__device__ __noinline__ void polish(Ctx& c, Solver& sv, Norms& nm)
 {
   PROF(4);
   const thip_osqp_settings& os = c.d->osqp;
@@ -5655,7 +5870,7 @@ __device__ void polish(Ctx& c, Solver& sv, Norms& nm)
 // One OSQPModel::optimize(): setup (bounds, rho, warm start, factor) + solve.
 // Scaled P/A/q must be current (build_and_scale).  Trust-box bounds from X.
 // Returns the CvxOptStatus.
-__device__ int qp_solve(Ctx& c, Solver& sv, bool pattern_equal)
+__device__ __noinline__ int qp_solve(Ctx& c, Solver& sv, bool pattern_equal)
 {
   PROF(12);
   const Layout& L = c.L;
