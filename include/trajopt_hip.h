@@ -50,8 +50,10 @@ extern "C" {
  * terms (thip_coll_term), single-waypoint problems on the generic path.  7: robot
  * self-collision link pairs (n_self_pairs / self_pair).  8: per link-pair collision
  * margins and coefficients (n_coll_pairs / coll_pairs).  9: the collision terms'
- * contact test type (coll_contact_test, thip_coll_term.contact_test). */
-#define THIP_ABI_VERSION 9
+ * contact test type (coll_contact_test, thip_coll_term.contact_test).  10: the
+ * CartVel terms (n_cvel / cvel_*, appended after the solver parameters: no
+ * earlier field moves). */
+#define THIP_ABI_VERSION 10
 
 #define THIP_MAX_DOF 16
 #define THIP_MAX_LINKS 32
@@ -64,6 +66,7 @@ extern "C" {
 #define THIP_MAX_JDT 8
 #define THIP_MAX_JVT 4
 #define THIP_MAX_TTT 2
+#define THIP_MAX_CVEL 4
 #define THIP_MAX_COLL_EXTRA 3
 #define THIP_MAX_SELF_PAIRS 64
 #define THIP_MAX_SELF_SPHERE_PAIRS 512
@@ -435,6 +438,33 @@ typedef struct thip_problem_desc {
 
   thip_sqp_params sqp;
   thip_osqp_settings osqp;
+
+  /* CartVelTermInfo (problem_description.cpp:1007-1076): a bound on the
+   * Cartesian step of a link's origin between consecutive waypoints.  Per step
+   * pair i in [first_step, last_step] over the joints of waypoints i and i + 1,
+   * CartVelErrCalculator (kinematic_terms.cpp:408-432) gives six rows,
+   *   err[0:3] = p_{i+1} - p_i - max_disp,  err[3:6] = p_i - p_{i+1} - max_disp
+   * (p the world translation of the link origin, no tcp), and
+   * CartVelJacCalculator (:372-406) their analytic jacobian
+   * [[-J_i, J_{i+1}], [J_i, -J_{i+1}]] (J the linear rows of the link's
+   * geometric jacobian).  is_cnt 0: one TrajOptCostFromErrFunc per pair, ABS;
+   * is_cnt 1: one TrajOptConstraintFromErrFunc per pair, INEQ.  The coefficient
+   * vector is empty: nothing is scaled.  The reference's loop reads waypoint
+   * last_step + 1 while its own check allows last_step = n_steps - 1; here
+   * last_step + 1 <= n_steps - 1 is required.
+   * Term order: costs follow the TotalTime costs, constraints the TotalTime
+   * constraints (collision stays last, as for every other table).  The table
+   * stands after the solver parameters so that no earlier field of the
+   * descriptor moved with ABI 10.  thip_create and thip_terms_create reject
+   * n_cvel > 0: the generic path runs the term on the device
+   * (thip_eval_cart_vel_all).  The oracle does not read this table: a
+   * descriptor with n_cvel > 0 must never be compared against it. */
+  int n_cvel;
+  int cvel_is_cnt[THIP_MAX_CVEL];
+  int cvel_link[THIP_MAX_CVEL];        /* chain link index, moved by a joint */
+  int cvel_first_step[THIP_MAX_CVEL];
+  int cvel_last_step[THIP_MAX_CVEL];
+  double cvel_max_disp[THIP_MAX_CVEL]; /* max_displacement */
 } thip_problem_desc;
 
 /* 1 when the descriptor's jdt terms can run in the fused sqp_kernel: every one a
@@ -626,9 +656,12 @@ int thip_debug_solve_layout(const thip_ctx* ctx, int* out, int n);
  *                           (:1267-1386), one term object per unit
  *                           (CollisionTermInfo::hatch, problem_description.cpp:1735-1858)
  * A thip_eval holds a descriptor (any n_steps in [1, THIP_EVAL_MAX_STEPS], up to
- * THIP_EVAL_MAX_PRIMS scene primitives, any term set: only the chain, CartPose and
- * collision fields are read) and the CartPose
- * targets and scenes of `batch` problems.  Synchronous; host arrays. */
+ * THIP_EVAL_MAX_PRIMS scene primitives, any term set: only the chain, CartPose,
+ * CartVel and collision fields are read) and the CartPose
+ * targets and scenes of `batch` problems.  Synchronous; host arrays.
+ * thip_eval_create validates the CartVel table before any device call: the link
+ * in [1, n_links) and moved by a joint, 0 <= first_step < last_step,
+ * last_step + 1 <= n_steps - 1, max_disp finite. */
 typedef struct thip_eval thip_eval;
 int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_eval** out);
 /* cart_targets [batch][n_cart][12], scene [batch][n_prims][16] (NULL when empty) */
@@ -646,6 +679,20 @@ int thip_eval_cart_pose(thip_eval* ev, int term, const double* q, double* err, d
  * the host loop evaluates all its CartPose terms at a new x with it instead of
  * one launch per term (sco::OptProb::prefetch). */
 int thip_eval_cart_pose_all(thip_eval* ev, const double* x, double* err, double* jac);
+/*   thip_eval_cart_vel_all <- CartVelErrCalculator / CartVelJacCalculator
+ *                             (trajopt/src/kinematic_terms.cpp:372-432), called through
+ *                             TrajOptCostFromErrFunc / TrajOptConstraintFromErrFunc
+ *                             (CartVelTermInfo::hatch, problem_description.cpp:1030-1076)
+ * Every step pair of every CartVel term of every problem at the joint
+ * trajectories x [batch][n_steps][n_dof], in one launch: err [batch][P][6], jac
+ * [batch][P][6][2 n_dof] (the columns of waypoint i, then of i + 1) or NULL for
+ * the error alone.  P = thip_eval_cart_vel_pairs(ev): the step pairs of all
+ * cvel terms, in term order and then ascending i.  Each waypoint's position and
+ * linear jacobian is computed once per (problem, term) and serves both pairs
+ * that touch it.  Needs no thip_eval_upload.  Bitwise repeatable; a problem's
+ * values do not depend on its position in the batch or on `batch`. */
+int thip_eval_cart_vel_pairs(const thip_eval* ev);
+int thip_eval_cart_vel_all(thip_eval* ev, const double* x, double* err, double* jac);
 /* Collision term `term` (0: the coll_* term when coll_enabled, then coll_extra[])
  * at trajectories x [batch][n_steps][n_dof]: every contact of every unit (a free
  * waypoint of [first, last] for DISCRETE, else a step pair) with its linearised

@@ -24,10 +24,18 @@
 //                      so the list comes out ordered without a sort.  The
 //                      arithmetic is oracle/src/collision.cpp's.
 //   coll_pack_kernel   concatenates the units' records per problem.
+//   cart_vel_kernel    CartVelErrCalculator / CartVelJacCalculator
+//                      (kinematic_terms.cpp:372-432) for every step pair of
+//                      every CartVel term: one 64-lane workgroup per (problem,
+//                      term), a lane per waypoint for the link origin and its
+//                      linear jacobian (kept in LDS, so the two pairs that
+//                      share a waypoint share its FK), then lanes over the
+//                      output elements.
 // fp64 throughout; integer/geometry work, no MFMA.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -714,6 +722,100 @@ __global__ __launch_bounds__(kEvBlock) void coll_pack_kernel(const double* stage
   if (threadIdx.x == 0)
     counts[b] = off;
 }
+
+// ------------------------------------------------------------------ CartVel
+// one CartVel term as the kernel reads it
+struct CvelTerm
+{
+  int link, first, last;  // step pairs first .. last over waypoints first .. last + 1
+  int pair_off;           // its first pair among the problem's P pairs
+  double max_disp;
+};
+
+constexpr int kCvChunk = 64;  // waypoints per pass (one per lane)
+// doubles per waypoint in LDS: p[3], then the linear jacobian rows Jp[3][D]; odd,
+// so that the lanes' strided writes spread over the banks
+__host__ __device__ constexpr int cvel_stride(int D) { return (3 + 3 * D) | 1; }
+static_assert(cvel_stride(THIP_MAX_DOF) == 51, "3 + 3 * THIP_MAX_DOF doubles per waypoint");
+
+// Every step pair of CartVel term k of problem b.  Waypoints first .. last + 1 are
+// taken kCvChunk at a time: lane w computes chain_fk / chain_jacobian of waypoint
+// t0 + w into LDS slot w + 1; slot 0 holds the last waypoint of the pass before.
+// After the barrier the pass's pairs (t0 - 1 .. t0 + n - 2, those >= first) are
+// written with the lanes over consecutive output elements.
+//   err [b][P][6]        (p1 - p0) - d, (p0 - p1) - d
+//   jac [b][P][6][2 D]   [[-J0, J1], [J0, -J1]]
+__global__ __launch_bounds__(kCvChunk) void cart_vel_kernel(const thip_chain* chain, const CvelTerm* terms, int batch,
+                                                            int n_cvel, int N, int P, const double* x, double* err,
+                                                            double* jac)
+{
+  const int item = blockIdx.x;
+  if (item >= batch * n_cvel)
+    return;
+  stage_chain_ev(chain);
+  const thip_chain& ch = s_chain;
+  const int b = item / n_cvel, k = item % n_cvel;
+  const CvelTerm tm = terms[k];
+  const int D = ch.n_dof, S = cvel_stride(D), lane = threadIdx.x;
+  __shared__ double s_wp[(kCvChunk + 1) * cvel_stride(THIP_MAX_DOF)];
+  const double* xb = x + static_cast<long long>(b) * N * D;
+  double* errb = err + (static_cast<long long>(b) * P + tm.pair_off) * 6;
+  double* jacb = jac ? jac + (static_cast<long long>(b) * P + tm.pair_off) * 12 * D : nullptr;
+  const int t_end = tm.last + 1;  // the last waypoint read (<= N - 1: thip_eval_create)
+  for (int t0 = tm.first; t0 <= t_end; t0 += kCvChunk)
+  {
+    const int n = min(kCvChunk, t_end - t0 + 1);
+    if (lane < n)
+    {
+      const double* q = xb + static_cast<long long>(t0 + lane) * D;
+      Pose T;
+      chain_fk(ch, q, tm.link, T);
+      double J[6 * THIP_MAX_DOF];
+      chain_jacobian(ch, q, tm.link, J);
+      double* w = s_wp + (lane + 1) * S;
+      w[0] = T.t[0];
+      w[1] = T.t[1];
+      w[2] = T.t[2];
+      for (int e = 0; e < 3 * D; ++e)
+        w[3 + e] = J[e];
+    }
+    __syncthreads();
+    // pairs of this pass: local pair l joins slots l and l + 1; l = 0 needs the
+    // carried waypoint, absent in the first pass
+    const int l0 = (t0 == tm.first) ? 1 : 0;
+    const int pair0 = t0 - 1 + l0 - tm.first;  // term-local index of the pass's first pair
+    const int np = n - l0;
+    for (int e = lane; e < np * 6; e += kCvChunk)
+    {
+      const int l = l0 + e / 6, r = e % 6;
+      const double* w0 = s_wp + l * S;
+      const double* w1 = w0 + S;
+      const double dp = (r < 3) ? w1[r] - w0[r] : w0[r - 3] - w1[r - 3];
+      errb[static_cast<long long>(pair0) * 6 + e] = dp - tm.max_disp;
+    }
+    if (jacb)
+    {
+      const int rowlen = 2 * D, per = 6 * rowlen;
+      for (int e = lane; e < np * per; e += kCvChunk)
+      {
+        const int l = l0 + e / per, rem = e % per;
+        const int r = rem / rowlen, c = rem % rowlen;
+        const int second = (c >= D) ? 1 : 0;
+        const double v = s_wp[(l + second) * S + 3 + (r % 3) * D + (c - second * D)];
+        const bool neg = (r < 3) == (second == 0);
+        jacb[static_cast<long long>(pair0) * per + e] = neg ? -v : v;
+      }
+    }
+    __syncthreads();
+    // carry the pass's last waypoint to slot 0
+    if (t0 + kCvChunk <= t_end)
+    {
+      for (int e = lane; e < S; e += kCvChunk)
+        s_wp[e] = s_wp[kCvChunk * S + e];
+      __syncthreads();
+    }
+  }
+}
 }  // namespace ev
 }  // namespace thip
 
@@ -734,6 +836,10 @@ struct thip_eval
   int* d_csteps = nullptr;      // per CartPose term: its waypoint
   double* d_err_all = nullptr;  // [batch][n_cart][6]
   double* d_jac_all = nullptr;  // [batch][n_cart][6][D]
+  CvelTerm* d_cvterms = nullptr;  // per CartVel term (cart_vel_kernel)
+  int cv_pairs = 0;               // P: step pairs over all CartVel terms
+  double* d_cv_err = nullptr;     // [batch][P][6]
+  double* d_cv_jac = nullptr;     // [batch][P][6][2 D]
   double* d_stage = nullptr;  // collision records per unit
   double* d_out = nullptr;    // packed records
   int* d_counts = nullptr;    // per unit, then per problem
@@ -832,6 +938,29 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
         desc->cart_source_link[k] >= ch.n_links || desc->cart_target_link[k] < 0 ||
         desc->cart_target_link[k] >= ch.n_links)
       return reject("bad CartPose term");
+  // CartVel terms: cart_vel_kernel reads waypoints first .. last + 1 of x [batch][N][D]
+  if (desc->n_cvel < 0 || desc->n_cvel > THIP_MAX_CVEL)
+    return reject("n_cvel out of range");
+  for (int k = 0; k < desc->n_cvel; ++k)
+  {
+    const std::string what = "CartVel term " + std::to_string(k) + ": ";
+    const int link = desc->cvel_link[k], first = desc->cvel_first_step[k], last = desc->cvel_last_step[k];
+    if (link < 1 || link >= ch.n_links)
+      return reject(what + "link " + std::to_string(link) + " outside [1, n_links)");
+    bool moved = false;
+    for (int i = link; i > 0; i = ch.is_tree ? ch.parent[i] : i - 1)
+      moved = moved || ch.joint_type[i] != THIP_JOINT_FIXED;
+    if (!moved)
+      return reject(what + "link " + std::to_string(link) + " is not moved by a joint (a fixed link)");
+    if (first < 0 || first >= last)
+      return reject(what + "need 0 <= first_step < last_step, got first_step " + std::to_string(first) +
+                    ", last_step " + std::to_string(last));
+    if (last > N - 2)
+      return reject(what + "last_step + 1 = " + std::to_string(static_cast<long long>(last) + 1) +
+                    " is past the last waypoint n_steps - 1 = " + std::to_string(N - 1));
+    if (!std::isfinite(desc->cvel_max_disp[k]))
+      return reject(what + "max_displacement is not finite");
+  }
   if (desc->n_coll_extra < 0 || desc->n_coll_extra > THIP_MAX_COLL_EXTRA)
     return reject("n_coll_extra out of range");
   if ((desc->coll_enabled || desc->n_coll_extra > 0) &&
@@ -988,6 +1117,24 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
         (e = hipMemcpy(ev->d_csteps, steps.data(), steps.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
       return hfail("hipMemcpy(CartPose terms)", e);
   }
+  // every CartVel term's arguments and the pair count (cart_vel_kernel)
+  if (d.n_cvel > 0)
+  {
+    std::vector<CvelTerm> cv(static_cast<size_t>(d.n_cvel));
+    for (int k = 0; k < d.n_cvel; ++k)
+    {
+      cv[static_cast<size_t>(k)] = { d.cvel_link[k], d.cvel_first_step[k], d.cvel_last_step[k], ev->cv_pairs,
+                                     d.cvel_max_disp[k] };
+      ev->cv_pairs += d.cvel_last_step[k] - d.cvel_first_step[k] + 1;
+    }
+    const size_t P = static_cast<size_t>(ev->cv_pairs);
+    if ((e = hipMalloc(&ev->d_cvterms, cv.size() * sizeof(CvelTerm))) != hipSuccess ||
+        (e = hipMalloc(&ev->d_cv_err, B * P * 6 * sizeof(double))) != hipSuccess ||
+        (e = hipMalloc(&ev->d_cv_jac, B * P * 12 * D * sizeof(double))) != hipSuccess)
+      return hfail("hipMalloc(CartVel terms)", e);
+    if ((e = hipMemcpy(ev->d_cvterms, cv.data(), cv.size() * sizeof(CvelTerm), hipMemcpyHostToDevice)) != hipSuccess)
+      return hfail("hipMemcpy(CartVel terms)", e);
+  }
   // per link-pair margins of each collision term (coefficients are the host's)
   for (size_t k = 0; k < ev->terms.size(); ++k)
   {
@@ -1098,6 +1245,38 @@ int thip_eval_cart_pose_all(thip_eval* ev, const double* x, double* err, double*
   return THIP_OK;
 }
 
+int thip_eval_cart_vel_pairs(const thip_eval* ev) { return ev ? ev->cv_pairs : -1; }
+
+int thip_eval_cart_vel_all(thip_eval* ev, const double* x, double* err, double* jac)
+{
+  if (!ev)
+    return THIP_E_INVALID;
+  const thip_problem_desc& d = ev->desc;
+  if (!x || !err)
+    return fail(ev, "thip_eval_cart_vel_all: null x / err");
+  if (d.n_cvel == 0)
+    return THIP_OK;
+  const int N = d.n_steps, D = d.chain.n_dof;
+  const size_t B = static_cast<size_t>(ev->batch), P = static_cast<size_t>(ev->cv_pairs);
+  hipError_t e;
+  if ((e = hipSetDevice(ev->device)) != hipSuccess)
+    return hipfail(ev, "hipSetDevice", e);
+  if ((e = hipMemcpyAsync(ev->d_x, x, B * N * D * sizeof(double), hipMemcpyHostToDevice, ev->stream)) != hipSuccess)
+    return hipfail(ev, "hipMemcpy(x)", e);
+  hipLaunchKernelGGL(cart_vel_kernel, dim3(static_cast<unsigned>(B * d.n_cvel)), dim3(kCvChunk), 0, ev->stream,
+                     ev->d_chain, ev->d_cvterms, ev->batch, d.n_cvel, N, ev->cv_pairs, ev->d_x, ev->d_cv_err,
+                     jac ? ev->d_cv_jac : nullptr);
+  if ((e = hipGetLastError()) != hipSuccess)
+    return hipfail(ev, "cart_vel_kernel launch", e);
+  if ((e = hipMemcpyAsync(err, ev->d_cv_err, B * P * 6 * sizeof(double), hipMemcpyDeviceToHost, ev->stream)) !=
+          hipSuccess ||
+      (jac && (e = hipMemcpyAsync(jac, ev->d_cv_jac, B * P * 12 * D * sizeof(double), hipMemcpyDeviceToHost,
+                                  ev->stream)) != hipSuccess) ||
+      (e = hipStreamSynchronize(ev->stream)) != hipSuccess)
+    return hipfail(ev, "cart_vel_kernel", e);
+  return THIP_OK;
+}
+
 int thip_eval_collision(thip_eval* ev, int term, const double* x, double* records, int cap, int* counts)
 {
   if (!ev)
@@ -1190,6 +1369,9 @@ void thip_eval_destroy(thip_eval* ev)
   hipFree(ev->d_csteps);
   hipFree(ev->d_err_all);
   hipFree(ev->d_jac_all);
+  hipFree(ev->d_cvterms);
+  hipFree(ev->d_cv_err);
+  hipFree(ev->d_cv_jac);
   hipFree(ev->d_stage);
   hipFree(ev->d_out);
   hipFree(ev->d_counts);

@@ -562,6 +562,9 @@ std::string validate_terms(const thip_problem_desc* d)
   if (d->use_time != 0 || d->n_jvt != 0 || d->n_ttt != 0 || d->n_fixed_dofs != 0)
     return std::string("time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs") +
            kHostLoop;
+  if (d->n_cvel != 0)
+    return std::string("CartVel terms (n_cvel > 0) run the generic path, its device evaluator thip_eval_cart_vel_all") +
+           kHostLoop;
   if (d->coll_enabled && d->coll_contact_test != THIP_CONTACT_ALL && d->coll_contact_test != THIP_CONTACT_FIRST &&
       d->coll_contact_test != THIP_CONTACT_CLOSEST)
     return "coll_contact_test is not a THIP_CONTACT_* value";

@@ -244,6 +244,10 @@ static int validate(const thip_problem_desc* d, std::string& why)
                  "lowered into the batched kernel: solve such a problem with sco::BasicTrustRegionSQP (the generic "
                  "path, GpuModel)",
            THIP_E_INVALID;
+  if (d->n_cvel != 0)
+    return why = "CartVel terms (n_cvel > 0) are not lowered into the batched kernel: solve such a problem with "
+                 "sco::BasicTrustRegionSQP (the generic path, device-evaluated terms and GpuModel)",
+           THIP_E_INVALID;
   if (d->coll_enabled && d->coll_contact_test != THIP_CONTACT_ALL && d->coll_contact_test != THIP_CONTACT_FIRST &&
       d->coll_contact_test != THIP_CONTACT_CLOSEST)
     return why = "coll_contact_test is not a THIP_CONTACT_* value", THIP_E_INVALID;

@@ -11,6 +11,9 @@
 //       sco::VectorOfVector / MatrixOfVector of the TrajOptCostFromErrFunc /
 //       TrajOptConstraintFromErrFunc that CartPoseTermInfo::hatch builds
 //       (problem_description.cpp:919-1005)
+//   CartVelDeviceErr / CartVelDeviceJac   CartVelErrCalculator /
+//       CartVelJacCalculator (kinematic_terms.cpp:372-432) of one step pair, as
+//       CartVelTermInfo::hatch builds them (problem_description.cpp:1030-1076)
 //   DeviceCollisionCost / DeviceCollisionConstraint   CollisionCost /
 //       CollisionConstraint (collision_terms.cpp:1267-1386), one per unit (a free
 //       waypoint for DISCRETE, a step pair otherwise) as
@@ -49,6 +52,16 @@ public:
   // q is bitwise term k's waypoint of that x
   void prefetchCart(const DblVec& x);
 
+  // step pair `pair` of the problem's CartVel terms (descriptor order, then
+  // ascending step: thip_eval_cart_vel_all's P axis) at q2 = [q_i ; q_i+1]:
+  // err[6], jac[6][2 n_dof] (row-major; may be null)
+  void cartVel(int pair, const DblVec& q2, double* err, double* jac);
+  // every pair at the full variable vector x in one launch; cartVel(pair, q2)
+  // then answers from it while q2 is bitwise the pair's two rows of that x
+  void prefetchCartVel(const DblVec& x);
+  // the first pair of CartVel term k on the P axis
+  int cartVelPairOffset(int k) const;
+
   // the contact records of one collision term (0 = the descriptor's coll_*,
   // then coll_extra[]) at the full variable vector x; W = 8 + 2 n_dof + 1
   struct Contacts
@@ -82,6 +95,15 @@ private:
     std::vector<double> jac;  // [n_cart][6][n_dof]
     bool valid = false;
   } cart_;
+  struct CartVelCache
+  {
+    DblVec q;                 // the joint trajectory [n_steps][n_dof] of the launch
+    std::vector<double> err;  // [P][6]
+    std::vector<double> jac;  // [P][6][2 n_dof]
+    bool valid = false;
+  } cvel_;
+  void launchCartVel(DblVec q);
+  int cartVelStep(int pair) const;  // the pair's first waypoint, -1 when out of range
   DblVec jointTrajectory(const DblVec& x) const;
   std::vector<std::vector<double>> pair_tab_;  // per term: pair_data.hpp table, empty = the term's own
 };
@@ -125,6 +147,41 @@ public:
   using sco::CostFromErrFunc::CostFromErrFunc;
 };
 class DeviceCartPoseConstraint : public sco::ConstraintFromErrFunc
+{
+public:
+  using sco::ConstraintFromErrFunc::ConstraintFromErrFunc;
+};
+
+class CartVelDeviceErr : public sco::VectorOfVector
+{
+public:
+  CartVelDeviceErr(std::shared_ptr<DeviceTermEvaluator> ev, int pair) : ev_(std::move(ev)), pair_(pair) {}
+  DblVec operator()(const DblVec& q2) const override;
+
+private:
+  std::shared_ptr<DeviceTermEvaluator> ev_;
+  int pair_;
+};
+
+class CartVelDeviceJac : public sco::MatrixOfVector
+{
+public:
+  CartVelDeviceJac(std::shared_ptr<DeviceTermEvaluator> ev, int pair) : ev_(std::move(ev)), pair_(pair) {}
+  sco::Mat operator()(const DblVec& q2) const override;
+
+private:
+  std::shared_ptr<DeviceTermEvaluator> ev_;
+  int pair_;
+};
+
+// TrajOptCostFromErrFunc / TrajOptConstraintFromErrFunc of one CartVel step pair
+// (problem_description.cpp:1044-1070), over the device calculators above
+class DeviceCartVelCost : public sco::CostFromErrFunc
+{
+public:
+  using sco::CostFromErrFunc::CostFromErrFunc;
+};
+class DeviceCartVelConstraint : public sco::ConstraintFromErrFunc
 {
 public:
   using sco::ConstraintFromErrFunc::ConstraintFromErrFunc;

@@ -11,11 +11,13 @@
 // term lowered runs the fused sqp_kernel (BatchTrustRegionSQP, batch_sqp.hpp,
 // or sco::BasicTrustRegionSQP as a batch of one), any other runs
 // sco::BasicTrustRegionSQP's host loop with each QP on the GPU (GpuModel).
-//  * Registered term types: joint_pos, joint_vel, joint_acc, joint_jerk,
-//    cart_pose, dynamic_cart_pose, collision.  cart_vel and total_time
-//    (problem_description.cpp:57-70) are registered too and their hatch()
-//    throws "not supported on the HIP path", so a JSON that uses them fails
-//    loudly rather than silently dropping a term.
+//  * Registered term types: every maker of the reference's registry
+//    (problem_description.cpp:57-70): joint_pos, joint_vel, joint_acc,
+//    joint_jerk, cart_pose, dynamic_cart_pose, cart_vel, collision,
+//    total_time.  What a term cannot do on the HIP path (a collision
+//    evaluator of type NONE) throws "not supported on the HIP path" from
+//    hatch(), so a JSON that asks for it fails loudly rather than silently
+//    dropping a term.
 //  * Environment / KinematicGroup stand in for tesseract's Environment and
 //    JointGroup (which are out of scope): a serial chain with link and joint
 //    names, joint limits, the current state, the collision spheres of the
@@ -265,6 +267,27 @@ struct DynamicCartPoseTermInfo : public CartPoseTermInfo
 {
   DynamicCartPoseTermInfo() { dynamic_ = true; }
   static TermInfo::Ptr create() { return std::make_shared<DynamicCartPoseTermInfo>(); }
+};
+
+// CartVelTermInfo (problem_description.hpp:389-411, problem_description.cpp:
+// 1007-1076): the origin of `link` moves at most max_displacement per axis
+// between consecutive waypoints, for the step pairs first_step .. last_step (the
+// pair i joins waypoints i and i + 1).  Not lowered into the batched kernel: its
+// hatch() adds one device-evaluated cost (ABS) or constraint (INEQ, named
+// "CartVel" as in the reference) per pair and records the term in the
+// descriptor's cvel table; the generic path runs it.
+// Deviation: the reference's hatch reads waypoint last_step + 1 while its
+// fromJson allows last_step = n_steps - 1, one row past the trajectory; here
+// fromJson and hatch refuse last_step + 1 > n_steps - 1.
+struct CartVelTermInfo : public TermInfo
+{
+  int first_step = -1, last_step = -1;
+  std::string link;  // the link's name (the reference's link_id), an active link of the group
+  double max_displacement = 0;
+  CartVelTermInfo() : TermInfo(TermType::TT_COST | TermType::TT_CNT) {}
+  void fromJson(ProblemConstructionInfo& pci, const Json::Value& v) override;
+  void hatch(TrajOptProb& prob) override;
+  static TermInfo::Ptr create() { return std::make_shared<CartVelTermInfo>(); }
 };
 
 // CollisionTermInfo (problem_description.cpp:1636-1858) with the

@@ -605,7 +605,10 @@ int traceCapacity(const sco::BasicTrustRegionSQPParameters& param)
 void TrajOptProb::prefetch(const DblVec& x)
 {
   if (device_terms_)
+  {
     device_terms_->prefetchCart(x);
+    device_terms_->prefetchCartVel(x);
+  }
 }
 
 bool TrajOptProb::solveNative(const sco::BasicTrustRegionSQPParameters& param, const DblVec& x0,

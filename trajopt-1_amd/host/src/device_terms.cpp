@@ -89,6 +89,83 @@ void DeviceTermEvaluator::cartPose(int k, const DblVec& q, double* err, double* 
     throw std::runtime_error(std::string("thip_eval_cart_pose: ") + thip_eval_last_error(ev_));
 }
 
+int DeviceTermEvaluator::cartVelPairOffset(int k) const
+{
+  const thip_problem_desc& d = prob_->desc();
+  int off = 0;
+  for (int i = 0; i < k && i < d.n_cvel; ++i)
+    off += d.cvel_last_step[i] - d.cvel_first_step[i] + 1;
+  return off;
+}
+
+int DeviceTermEvaluator::cartVelStep(int pair) const
+{
+  const thip_problem_desc& d = prob_->desc();
+  for (int k = 0; k < d.n_cvel && pair >= 0; ++k)
+  {
+    const int n = d.cvel_last_step[k] - d.cvel_first_step[k] + 1;
+    if (pair < n)
+      return d.cvel_first_step[k] + pair;
+    pair -= n;
+  }
+  return -1;
+}
+
+void DeviceTermEvaluator::launchCartVel(DblVec q)
+{
+  const std::size_t D = static_cast<std::size_t>(prob_->GetNumDOF());
+  const std::size_t P = static_cast<std::size_t>(thip_eval_cart_vel_pairs(ev_));
+  cvel_.valid = false;
+  cvel_.err.resize(P * 6);
+  cvel_.jac.resize(P * 12 * D);
+  if (thip_eval_cart_vel_all(ev_, q.data(), cvel_.err.data(), cvel_.jac.data()) != THIP_OK)
+    throw std::runtime_error(std::string("thip_eval_cart_vel_all: ") + thip_eval_last_error(ev_));
+  cvel_.q = std::move(q);
+  cvel_.valid = true;
+}
+
+void DeviceTermEvaluator::prefetchCartVel(const DblVec& x)
+{
+  if (prob_->desc().n_cvel == 0)
+    return;
+  ensure();
+  DblVec q = jointTrajectory(x);
+  if (cvel_.valid && cvel_.q == q)
+    return;
+  launchCartVel(std::move(q));
+}
+
+void DeviceTermEvaluator::cartVel(int pair, const DblVec& q2, double* err, double* jac)
+{
+  ensure();
+  const std::size_t D = static_cast<std::size_t>(prob_->GetNumDOF());
+  if (q2.size() != 2 * D)
+    throw std::runtime_error("CartVel evaluation: expected " + std::to_string(2 * D) + " joint values");
+  const int t = cartVelStep(pair);
+  if (t < 0)
+    throw std::runtime_error("CartVel evaluation: pair out of range");
+  const long row = static_cast<long>(static_cast<std::size_t>(t) * D);
+  if (!cvel_.valid || !std::equal(q2.begin(), q2.end(), cvel_.q.begin() + row))
+  {
+    // not the prefetched x: one launch at the last trajectory (the initial one
+    // before any launch) with this pair's two rows replaced
+    DblVec q = cvel_.q;
+    if (q.size() != static_cast<std::size_t>(prob_->GetNumSteps()) * D)
+    {
+      q.clear();
+      for (const DblVec& r : prob_->GetInitTraj())  // the joint columns
+        q.insert(q.end(), r.begin(), r.begin() + static_cast<long>(D));
+    }
+    std::copy(q2.begin(), q2.end(), q.begin() + row);
+    launchCartVel(std::move(q));
+  }
+  const std::size_t pu = static_cast<std::size_t>(pair);
+  std::copy(cvel_.err.begin() + static_cast<long>(pu * 6), cvel_.err.begin() + static_cast<long>(pu * 6 + 6), err);
+  if (jac)
+    std::copy(cvel_.jac.begin() + static_cast<long>(pu * 12 * D), cvel_.jac.begin() + static_cast<long>((pu + 1) * 12 * D),
+              jac);
+}
+
 const DeviceTermEvaluator::Contacts& DeviceTermEvaluator::collision(int term, const DblVec& x)
 {
   ensure();
@@ -163,6 +240,26 @@ sco::Mat CartPoseDeviceJac::operator()(const DblVec& q) const
   for (int r = 0; r < J.rows; ++r)
     for (int j = 0; j < D; ++j)
       J(r, j) = jac[static_cast<std::size_t>(indices_[static_cast<std::size_t>(r)] * D + j)];
+  return J;
+}
+
+DblVec CartVelDeviceErr::operator()(const DblVec& q2) const
+{
+  DblVec err(6);
+  ev_->cartVel(pair_, q2, err.data(), nullptr);
+  return err;
+}
+
+sco::Mat CartVelDeviceJac::operator()(const DblVec& q2) const
+{
+  const int W = static_cast<int>(q2.size());
+  double err[6];
+  std::vector<double> jac(static_cast<std::size_t>(6 * W));
+  ev_->cartVel(pair_, q2, err, jac.data());
+  sco::Mat J(6, W);
+  for (int r = 0; r < 6; ++r)
+    for (int j = 0; j < W; ++j)
+      J(r, j) = jac[static_cast<std::size_t>(r * W + j)];
   return J;
 }
 

@@ -1,7 +1,7 @@
 // Host front door: ProblemConstructionInfo::fromJson, the TermInfo registry,
 // hatch() lowering and ConstructProblem, restating
 // trajopt/src/problem_description.cpp:36-598 (+ the term infos at
-// :843-1005, :1078-1391, :1636-1858) over the C-ABI descriptor.
+// :843-1076, :1078-1391, :1636-1858) over the C-ABI descriptor.
 #include "trajopt_amd/problem_description.hpp"
 
 #include <algorithm>
@@ -56,32 +56,13 @@ bool doubleEquals(double a, double b) { return std::fabs(a - b) < 1e-5; }  // tr
   throw std::runtime_error(what + " is not supported on the HIP path");
 }
 
-// A registered maker whose lowering does not exist on the HIP path.
-struct UnsupportedTermInfo : public trajopt::TermInfo
-{
-  std::string type;
-  explicit UnsupportedTermInfo(std::string t)
-    : TermInfo(trajopt::TermType::TT_COST | trajopt::TermType::TT_CNT | trajopt::TermType::TT_USE_TIME)
-    , type(std::move(t))
-  {
-  }
-  void fromJson(trajopt::ProblemConstructionInfo&, const Json::Value&) override {}
-  void hatch(trajopt::TrajOptProb&) override { unsupported("term type '" + type + "'"); }
-};
-template <const char* kName>
-trajopt::TermInfo::Ptr makeUnsupported()
-{
-  return std::make_shared<UnsupportedTermInfo>(kName);
-}
-constexpr char kCartVel[] = "cart_vel";
-
 // problem_description.cpp:57-70
 void RegisterMakers()
 {
   gRegisteredMakers = true;  // first: RegisterMaker() below checks it
   trajopt::TermInfo::RegisterMaker("dynamic_cart_pose", &trajopt::DynamicCartPoseTermInfo::create);
   trajopt::TermInfo::RegisterMaker("cart_pose", &trajopt::CartPoseTermInfo::create);
-  trajopt::TermInfo::RegisterMaker("cart_vel", &makeUnsupported<kCartVel>);
+  trajopt::TermInfo::RegisterMaker("cart_vel", &trajopt::CartVelTermInfo::create);
   trajopt::TermInfo::RegisterMaker("joint_pos", &trajopt::JointPosTermInfo::create);
   trajopt::TermInfo::RegisterMaker("joint_vel", &trajopt::JointVelTermInfo::create);
   trajopt::TermInfo::RegisterMaker("joint_acc", &trajopt::JointAccTermInfo::create);
@@ -961,6 +942,85 @@ void CartPoseTermInfo::hatch(TrajOptProb& prob)
     prob.addLoweredCost(std::make_shared<DeviceCartPoseCost>(f, dfdx, vars, coeffs, sco::ABS, name), THIP_TERM_CART, k);
 }
 
+// ------------------------------------------------------------ CartVel
+// problem_description.cpp:1007-1028.  One deviation: the reference's hatch reads
+// waypoint last_step + 1 while this check of its allows last_step = n_steps - 1,
+// one row past the trajectory; here last_step + 1 must be a waypoint.
+void CartVelTermInfo::fromJson(ProblemConstructionInfo& pci, const Json::Value& v)
+{
+  if (!v.isMember("params"))
+    throw std::runtime_error("CartVelTermInfo: missing params");
+  const Json::Value& params = v["params"];
+  json_marshal::childFromJson(params, first_step, "first_step");
+  json_marshal::childFromJson(params, last_step, "last_step");
+  json_marshal::childFromJson(params, max_displacement, "max_displacement");
+  const int n_steps = pci.basic_info.n_steps;
+  if (!(first_step >= 0 && first_step <= n_steps - 1 && first_step < last_step))
+    throw std::runtime_error("CartVelTermInfo: need 0 <= first_step < last_step, got first_step " +
+                             std::to_string(first_step) + ", last_step " + std::to_string(last_step));
+  if (!(last_step > 0 && last_step <= n_steps - 2))
+    throw std::runtime_error("CartVelTermInfo: last_step " + std::to_string(last_step) + " reads waypoint " +
+                             std::to_string(static_cast<long long>(last_step) + 1) +
+                             ", past the last waypoint n_steps - 1 = " +
+                             std::to_string(n_steps - 1));
+  json_marshal::childFromJson(params, link, "link");
+  if (!pci.kin->isActiveLinkId(link))
+    throw std::runtime_error("invalid link name: " + link);
+  const char* all_fields[] = { "first_step", "last_step", "max_displacement", "link" };
+  ensure_only_members(params, all_fields, sizeof(all_fields) / sizeof(char*));
+}
+
+// problem_description.cpp:1030-1076: per step pair one TrajOptCostFromErrFunc (ABS) or
+// TrajOptConstraintFromErrFunc (INEQ, "CartVel") over the joints of waypoints i and
+// i + 1 with an empty coefficient vector, the error and its jacobian evaluated on
+// the device (thip_eval_cart_vel_all)
+void CartVelTermInfo::hatch(TrajOptProb& prob)
+{
+  if (any(term_type & TermType::TT_USE_TIME))
+    // (the reference logs an error and adds nothing)
+    throw std::runtime_error("CartVelTermInfo '" + name + "': the use_time version of this term has not been defined");
+  const bool is_cost = any(term_type & TermType::TT_COST);
+  if (!is_cost && !any(term_type & TermType::TT_CNT))
+    throw std::runtime_error("CartVelTermInfo '" + name + "' does not have a valid term_type defined");
+  const auto kin = prob.GetKin();
+  const int n_steps = prob.GetNumSteps(), n_dof = prob.GetNumDOF();
+  if (!kin->isActiveLinkId(link))
+    throw std::runtime_error("invalid link name: " + link);
+  if (first_step < 0 || first_step >= last_step)
+    throw std::runtime_error("CartVelTermInfo: need 0 <= first_step < last_step, got first_step " +
+                             std::to_string(first_step) + ", last_step " + std::to_string(last_step));
+  if (last_step > n_steps - 2)
+    throw std::runtime_error("CartVelTermInfo: last_step " + std::to_string(last_step) + " reads waypoint " +
+                             std::to_string(static_cast<long long>(last_step) + 1) +
+                             ", past the last waypoint n_steps - 1 = " +
+                             std::to_string(n_steps - 1));
+  if (!std::isfinite(max_displacement))
+    throw std::runtime_error("CartVelTermInfo: max_displacement is not finite");
+  thip_problem_desc& d = prob.desc();
+  if (d.n_cvel >= THIP_MAX_CVEL)
+    unsupported("more than " + std::to_string(THIP_MAX_CVEL) + " CartVel terms");
+  const int k = d.n_cvel++;
+  d.cvel_is_cnt[k] = is_cost ? 0 : 1;
+  d.cvel_link[k] = kin->linkIndex(link);
+  d.cvel_first_step[k] = first_step;
+  d.cvel_last_step[k] = last_step;
+  d.cvel_max_disp[k] = max_displacement;
+  const int pair0 = prob.deviceTerms()->cartVelPairOffset(k);
+  for (int i = first_step; i <= last_step; ++i)
+  {
+    const int pair = pair0 + (i - first_step);
+    auto f = std::make_shared<CartVelDeviceErr>(prob.deviceTerms(), pair);
+    auto dfdx = std::make_shared<CartVelDeviceJac>(prob.deviceTerms(), pair);
+    sco::VarVector vars = prob.GetVarRow(i, 0, n_dof);
+    const sco::VarVector next = prob.GetVarRow(i + 1, 0, n_dof);
+    vars.insert(vars.end(), next.begin(), next.end());
+    if (is_cost)
+      prob.addCost(std::make_shared<DeviceCartVelCost>(f, dfdx, vars, DblVec(), sco::ABS, name));
+    else
+      prob.addConstraint(std::make_shared<DeviceCartVelConstraint>(f, dfdx, vars, DblVec(), sco::INEQ, "CartVel"));
+  }
+}
+
 // ------------------------------------------------------------ Collision
 void CollisionTermInfo::fromJson(ProblemConstructionInfo& pci, const Json::Value& v)
 {
@@ -1471,7 +1531,7 @@ bool TrajOptProb::lowerable() const
   // scene primitives, and no term it does not lower
   return desc_.n_steps >= 2 && desc_.n_steps <= THIP_MAX_STEPS && desc_.n_prims <= THIP_MAX_PRIMS &&
          thip_jdt_fused(&desc_) && desc_.n_jvt == 0 && desc_.n_ttt == 0 && !desc_.use_time && desc_.n_fixed_dofs == 0 &&
-         desc_.n_coll_extra == 0 && unloweredTerms().empty();
+         desc_.n_cvel == 0 && desc_.n_coll_extra == 0 && unloweredTerms().empty();
 }
 
 LoweredProblem TrajOptProb::lowered() const

@@ -46,6 +46,8 @@ std::string whyNotLowerable(const TrajOptProb& prob)
     note("more than one collision term (coll_extra)");
   if (d.use_time || d.n_jvt > 0 || d.n_ttt > 0 || d.n_fixed_dofs > 0)
     note("time parameterisation (use_time, time terms) or fixed dofs");
+  if (d.n_cvel > 0)
+    note("CartVel terms (cart_vel), which the generic path evaluates on the device");
   if (!thip_jdt_fused(&d))
     note("a JointVel constraint / JointAcc / JointJerk term that is not the fused JointAccEqCost (jdt)");
   const std::string terms = prob.unloweredTerms();

@@ -10,7 +10,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-ABI_VERSION = 9  # THIP_ABI_VERSION
+ABI_VERSION = 10  # THIP_ABI_VERSION
 CONTACT_ALL, CONTACT_FIRST, CONTACT_CLOSEST = 0, 1, 2  # THIP_CONTACT_* (collision contact_test_type)
 MAX_DOF = 16
 MAX_LINKS = 32
@@ -23,6 +23,7 @@ MAX_JVX = 4
 MAX_JDT = 8
 MAX_JVT = 4
 MAX_TTT = 2
+MAX_CVEL = 4
 MAX_COLL_EXTRA = 3
 MAX_SELF_PAIRS = 64
 MAX_SELF_SPHERE_PAIRS = 512
@@ -235,6 +236,13 @@ class ProblemDesc(C.Structure):
         ("coll_pairs", CollPair * MAX_COLL_PAIRS),
         ("sqp", SqpParams),
         ("osqp", OsqpSettings),
+        # CartVel terms (ABI 10): after the solver parameters, so no earlier field moved
+        ("n_cvel", C.c_int),
+        ("cvel_is_cnt", C.c_int * MAX_CVEL),
+        ("cvel_link", C.c_int * MAX_CVEL),
+        ("cvel_first_step", C.c_int * MAX_CVEL),
+        ("cvel_last_step", C.c_int * MAX_CVEL),
+        ("cvel_max_disp", C.c_double * MAX_CVEL),
     ]
 
     def __init__(self, *a, **kw):
@@ -423,6 +431,10 @@ def _declare(lib):
     lib.thip_eval_upload.restype = C.c_int
     lib.thip_eval_cart_pose.argtypes = [vp, C.c_int, dp, dp, dp]
     lib.thip_eval_cart_pose.restype = C.c_int
+    lib.thip_eval_cart_vel_pairs.argtypes = [vp]
+    lib.thip_eval_cart_vel_pairs.restype = C.c_int
+    lib.thip_eval_cart_vel_all.argtypes = [vp, dp, dp, dp]
+    lib.thip_eval_cart_vel_all.restype = C.c_int
     lib.thip_eval_collision.argtypes = [vp, C.c_int, dp, dp, C.c_int, P(C.c_int)]
     lib.thip_eval_collision.restype = C.c_int
     lib.thip_eval_destroy.argtypes = [vp]

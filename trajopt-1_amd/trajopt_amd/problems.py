@@ -346,6 +346,25 @@ def with_joint_acc(wl, coeff=1.0, target=0.0, first_step=0, last_step=-1):
     return wl
 
 
+def with_cart_vel(wl, link, first_step, last_step, max_displacement, is_cnt=True):
+    """Add a CartVel term to every problem of wl (CartVelTermInfo,
+    problem_description.cpp:1007-1076): per step pair i in [first_step, last_step]
+    the origin of chain link `link` moves at most max_displacement per axis between
+    waypoints i and i + 1 (an INEQ constraint, or an ABS cost with is_cnt=False).
+    Only the generic path runs it (thip_eval_cart_vel_all); the oracle does not
+    read the table, so such a workload is never compared against it."""
+    d = wl.desc
+    k = d.n_cvel
+    assert k < abi.MAX_CVEL
+    d.cvel_is_cnt[k] = 1 if is_cnt else 0
+    d.cvel_link[k] = link
+    d.cvel_first_step[k] = first_step
+    d.cvel_last_step[k] = last_step
+    d.cvel_max_disp[k] = max_displacement
+    d.n_cvel = k + 1
+    return wl
+
+
 def with_dynamic_target(wl, link=3):
     """Make every CartPose term of wl a DynamicCartPose term (both frames active,
     DynamicCartPoseTermInfo, problem_description.cpp:683-842): the target is chain link

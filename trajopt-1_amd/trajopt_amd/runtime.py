@@ -231,6 +231,19 @@ class TermEvaluator:
                     "thip_eval_cart_pose")
         return err, J
 
+    def cart_vel(self, x, jac=True):
+        """x [B, N, D] -> err [B, P, 6], jac [B, P, 6, 2 D] (or None): every step
+        pair of every CartVel term, in term order and then ascending step
+        (thip_eval_cart_vel_all)."""
+        B, D = self.wl.batch, self.wl.n_dof
+        P = self.lib.thip_eval_cart_vel_pairs(self.ev)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(B, self.wl.desc.n_steps, D)
+        err = np.zeros((B, P, 6))
+        J = np.zeros((B, P, 6, 2 * D)) if jac else None
+        self._check(self.lib.thip_eval_cart_vel_all(self.ev, _dp(x), _dp(err), None if J is None else _dp(J)),
+                    "thip_eval_cart_vel_all")
+        return err, J
+
     def collision(self, term, x, cap=4096):
         """x [B, N, D] -> list of record arrays [n_b, 8 + 2 D + 1]."""
         B, D = self.wl.batch, self.wl.n_dof
