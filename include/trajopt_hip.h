@@ -945,6 +945,80 @@ int thip_qp_warm_start(thip_qp* qp, const double* x, const double* y);
 /* osqp_solve from the kept iterates (warm_starting) or from zero: x [batch][n], y [batch][m] (may be NULL) */
 int thip_qp_solve_resident(thip_qp* qp, double* x, double* y, thip_qp_info* info);
 
+/* ------------------------------------------------------- Collision sets
+ * The rows of trajopt_ifopt's fixed-size DiscreteCollisionConstraint over a
+ * SingleTimestepCollisionEvaluator (trajopt_ifopt/src/constraints/collision/
+ * discrete_collision_evaluators.cpp:89-188, discrete_collision_constraint.cpp:
+ * 91-141, trajopt_common/src/collision_utils.cpp:116-190, collision_types.cpp:
+ * 173-247, weighted_average_methods.cpp:31-68) for every node of
+ * [first_step, last_step] of every problem of a batch, in one launch, on the
+ * primitive collision model of the collision terms (THIP_PRIM_*).
+ *
+ * From the descriptor a thip_csets reads only the chain, the robot spheres, the
+ * self-collision pairs, n_prims, n_steps and the coll_pairs entries whose term
+ * is 0: per link-pair (margin, coeff) overrides of the config's margin and
+ * coeff.  n_steps in [1, THIP_EVAL_MAX_STEPS], n_prims in
+ * [0, THIP_EVAL_MAX_PRIMS].  A descriptor without robot spheres is refused.
+ *
+ * Candidates at node t, q = x[b][t]: every robot sphere against every scene
+ * primitive, then every enabled self sphere pair; each is one single-state
+ * contact with the distance, normal and contact points of the DISCRETE
+ * evaluator.  A contact is kept when its pair's coefficient is not zero
+ * (|coeff| <= 1e-6 of an override drops the pair) and distance <=
+ * margin(pair) + margin_buffer.  Each kept contact is one set (the reference's
+ * (link pair, shape pair) group holds one result in this model) with
+ * error = margin(pair) - distance.
+ *
+ * Row order -- this build's fixed choice of an order the reference leaves open
+ * (it sorts by error only when there are more than max_num_cnt sets, and
+ * follows hash-bucket order below that): always error descending, ties by
+ * (link, other, sphere, other_sphere) ascending, where a scene contact has
+ * other = the primitive index and other_sphere = -1, and a self contact has
+ * other = -1 - (link of the second sphere) and other_sphere = the second
+ * sphere.  The first R = max_num_cnt rows are kept.
+ *
+ * Outputs, host arrays, u = t - first_step, n = last_step - first_step + 1 (any
+ * may be NULL):
+ *   values [batch][n][R]         error; -margin_buffer in rows >= counts
+ *   jac    [batch][n][R][n_dof]  minus the distance gradient in q; for a self
+ *                                pair with both links moved by joints minus HALF
+ *                                the sum of the two links' gradients (the
+ *                                weighted average counts the set's weight once
+ *                                per link); zero when error + margin_buffer <= 0
+ *                                and in rows >= counts
+ *   coeffs [batch][n][R]         coeff(pair); 1 in rows >= counts
+ *   counts [batch][n]            sets before truncation
+ *   keys   [batch][n][R][4]      (link, other, sphere, other_sphere); -1 in rows >= counts
+ * Bitwise repeatable; a problem's rows do not depend on its position in the
+ * batch or on `batch`. */
+#define THIP_CSETS_MAX_ROWS 64
+typedef struct thip_csets_config {
+  double margin, coeff, margin_buffer; /* TrajOptCollisionConfig(margin, coeff), collision_margin_buffer */
+  int max_num_cnt;                     /* rows per node, 1 .. THIP_CSETS_MAX_ROWS */
+  int first_step, last_step;           /* the nodes that carry a set, inclusive, both in [0, n_steps) */
+} thip_csets_config;
+
+typedef struct thip_csets thip_csets;
+void thip_default_csets_config(thip_csets_config* c); /* margin 0, coeff 1, buffer 0, one row, node 0 */
+int thip_sizeof_csets_config(void);
+/* Validates cfg and every descriptor field read before any device call. */
+int thip_csets_create(int device, const thip_problem_desc* desc, const thip_csets_config* cfg, int batch,
+                      thip_csets** out);
+/* scene [batch][n_prims][16] (NULL when n_prims = 0): host / device pointer */
+int thip_csets_upload(thip_csets* cs, const double* scene);
+int thip_csets_upload_device(thip_csets* cs, const double* d_scene);
+int thip_csets_nodes(const thip_csets* cs); /* last_step - first_step + 1 */
+/* x [batch][n_steps][n_dof].  Synchronous.  The _device variant reads
+ * trajectories already on the device. */
+int thip_csets_run(thip_csets* cs, const double* x, double* values, double* jac, double* coeffs, int* counts,
+                   int* keys);
+int thip_csets_run_device(thip_csets* cs, const double* d_x, double* values, double* jac, double* coeffs, int* counts,
+                          int* keys);
+/* The kernel of the last run, HIP events on the object's stream (milliseconds; < 0: none). */
+double thip_csets_last_ms(thip_csets* cs);
+void thip_csets_destroy(thip_csets* cs);
+const char* thip_csets_last_error(thip_csets* cs); /* NULL: the last thip_csets_create failure */
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,69 @@ int thost_tsqp_solve(const tsqp_spec* spec, int device, double* x, tsqp_result* 
 int thost_tsqp_sizeof_spec(void);
 int thost_tsqp_sizeof_result(void);
 
+/* The kinematic sets of the same front end (trajopt_ifopt::CartPosConstraint and
+ * the fixed-size trajopt_ifopt::DiscreteCollisionConstraint over a
+ * SingleTimestepCollisionEvaluator, trajopt-1_amd/host/include/trajopt_ifopt/
+ * constraints/), their values and jacobians from the device: a tsqp_kin_spec
+ * adds them to the joint terms of a tsqp_spec, on the built-in environment of
+ * `manip` (Environment::builtin: the PR2 groups, or spherebot's "manipulator")
+ * with `n_prims` more scene primitives.  spec->n_dof must be the group's. */
+#define TSQP_KIN_MAX_CART 16
+#define TSQP_KIN_MAX_COLL 4
+#define TSQP_KIN_MAX_PRIMS 32
+#define TSQP_KIN_NAME_LEN 64
+typedef struct tsqp_cart_term {
+  int node;
+  int penalty;                        /* TSQP_CONSTRAINT / SQUARED / ABSOLUTE / HINGE */
+  int analytic_jacobian;              /* 1: use_numeric_differentiation = false, which the set refuses at update() */
+  int pad_;
+  char source_frame[TSQP_KIN_NAME_LEN], target_frame[TSQP_KIN_NAME_LEN];
+  double source_offset[12], target_offset[12]; /* 3x4 row-major [R | t] */
+  double coeffs[6];                   /* a zero coefficient drops the component's row */
+  double lower[6], upper[6];          /* bounds of the six error components (a range splits into two rows) */
+} tsqp_cart_term;
+typedef struct tsqp_coll_term {
+  int first, last;                    /* one DiscreteCollisionConstraint per node of first..last, one evaluator */
+  int penalty;
+  int max_num_cnt, fixed_sparsity;
+  double margin, coeff, buffer;       /* TrajOptCollisionConfig(margin, coeff), collision_margin_buffer */
+} tsqp_coll_term;
+typedef struct tsqp_kin_spec {
+  char manip[TSQP_KIN_NAME_LEN];
+  int n_prims;
+  double prims[TSQP_KIN_MAX_PRIMS][16]; /* THIP_PRIM_* records appended to the environment's scene */
+  int n_cart;
+  tsqp_cart_term cart[TSQP_KIN_MAX_CART];
+  int n_coll;
+  tsqp_coll_term coll[TSQP_KIN_MAX_COLL];
+} tsqp_kin_spec;
+/* thost_tsqp_solve with the kinematic sets added after the joint terms (the
+ * CartPos sets, then each collision term's nodes) */
+int thost_tsqp_solve_kin(const tsqp_spec* spec, const tsqp_kin_spec* kin, int device, double* x, tsqp_result* result,
+                         char* err, int err_len);
+/* The same sets without a solve: for each of the n_x variable vectors xs
+ * [n_x][n_nodes][n_dof], set in turn with TrajOptQPProblem::setVariables, every
+ * set's getValues, dense getJacobian and getCoefficients, rows concatenated in
+ * set order (joint terms, CartPos sets, collision nodes):
+ *   n_sets, set_rows [cap_sets]          the sets and their row counts
+ *   values, coeffs [n_x][cap_rows]       jac [n_x][cap_rows][n_nodes * n_dof]
+ *   lower, upper [cap_rows]              getBounds (+-inf as +-HUGE_VAL)
+ *   probe_q [n_dof] (may be NULL) -> probe_values [cap_rows]: after the last x,
+ *     every CartPos set's calcValues(probe_q) in its rows (other rows untouched),
+ *     asked while the variables still hold the last x
+ *   launches [2]                         device launches of the CartPos evaluator and of the collision
+ *                                        evaluators over the whole call (the probe's included)
+ * Any output may be NULL; more than cap_sets sets or cap_rows rows is an error.
+ * With n_x = 0 the sets are only constructed (their validation, rows and bounds):
+ * no device call is made. */
+int thost_tsqp_eval_kin(const tsqp_spec* spec, const tsqp_kin_spec* kin, int device, const double* xs, int n_x,
+                        int* n_sets, int* set_rows, int cap_sets, double* values, double* jac, double* coeffs,
+                        double* lower, double* upper, int cap_rows, const double* probe_q, double* probe_values,
+                        long long* launches, char* err, int err_len);
+int thost_tsqp_sizeof_kin_spec(void);
+int thost_tsqp_sizeof_cart_term(void);
+int thost_tsqp_sizeof_coll_term(void);
+
 #ifdef __cplusplus
 }
 #endif

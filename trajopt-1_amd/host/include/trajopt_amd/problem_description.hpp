@@ -112,7 +112,8 @@ public:
   bool isCollisionAllowed(const std::string& a, const std::string& b) const;
 
   // PR2 arms (groups "right_arm", "left_arm": torso_lift_link ->
-  // *_gripper_tool_frame, and "both_arms", joint data of
+  // *_gripper_tool_frame, "both_arms", and "torso_right_arm": base_link -> the torso
+  // joint -> the right arm; joint data of
   // trajopt_common/data/arm_around_table.urdf), zero state, the 14-sphere
   // per-arm collision model of trajopt_amd/scene.py, empty scene.
   static Ptr makePR2();

@@ -3,8 +3,10 @@
 // vector per node here); NodesVariables flattens them into the optimisation
 // vector, a Var's getIndex() is its first column there.
 #pragma once
+#include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "trajopt_ifopt/core/bounds.h"
@@ -13,6 +15,7 @@
 namespace trajopt_ifopt
 {
 class NodesVariables;
+class Node;
 
 class Var
 {
@@ -24,9 +27,13 @@ public:
   Index size() const { return static_cast<Index>(values_.size()); }
   const VectorXd& value() const { return values_; }
   const std::vector<Bounds>& getBounds() const { return bounds_; }
+  // the node that holds the var (null for a free-standing Var)
+  const Node* getParent() const { return parent_; }
 
 private:
   friend class NodesVariables;
+  friend class Node;
+  const Node* parent_ = nullptr;
   std::string name_;
   std::vector<std::string> child_names_;
   VectorXd values_;
@@ -42,8 +49,12 @@ public:
                                     const VectorXd& values, const std::vector<Bounds>& bounds);
   const std::string& getName() const { return name_; }
   const std::vector<std::shared_ptr<Var>>& getVars() const { return vars_; }
+  // the variable set the node was moved into (null before that)
+  const NodesVariables* getParent() const { return parent_; }
 
 private:
+  friend class NodesVariables;
+  const NodesVariables* parent_ = nullptr;
   std::string name_;
   std::vector<std::shared_ptr<Var>> vars_;
 };
@@ -60,8 +71,14 @@ public:
   std::vector<Bounds> getBounds() const;
   // changes whenever setVariables changes a value (TrajOptQPProblem skips term updates otherwise)
   std::size_t getHash() const { return hash_; }
+  // every Var in variable-vector order (a Var's place here is its waypoint for the device evaluators)
+  const std::vector<std::shared_ptr<Var>>& getVars() const { return vars_; }
+  // An object that lives as long as the variable set and is shared by the sets
+  // over it: the device evaluator of the kinematic sets, one per (device, group).
+  std::shared_ptr<void>& attachment(int device, const void* key) const { return attachments_[{ device, key }]; }
 
 private:
+  mutable std::map<std::pair<int, const void*>, std::shared_ptr<void>> attachments_;
   std::string name_;
   std::vector<std::unique_ptr<Node>> nodes_;
   std::vector<std::shared_ptr<Var>> vars_;

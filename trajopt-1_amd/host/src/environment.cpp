@@ -56,8 +56,10 @@ void armRows(bool left, std::vector<JointRow>& rows)
 }
 
 // A joint group of one or two arms off torso_lift_link (each arm a branch of
-// the tree rooted at the group's link 0).
-KinematicGroup makeGroup(const std::string& name, const std::vector<bool>& arms_left)
+// the tree rooted at the group's link 0).  with_torso: the chain starts at
+// base_link and torso_lift_joint (arm_around_table.urdf:735-745, prismatic along
+// z, limits [0, 0.33]) comes first, then the one arm -- robots.py's torso_right_arm.
+KinematicGroup makeGroup(const std::string& name, const std::vector<bool>& arms_left, bool with_torso = false)
 {
   KinematicGroup g;
   g.name = name;
@@ -72,11 +74,19 @@ KinematicGroup makeGroup(const std::string& name, const std::vector<bool>& arms_
   c.joint_dof[0] = -1;
   c.parent[0] = 0;
   c.is_tree = arms_left.size() > 1 ? 1 : 0;
-  g.link_names.push_back("torso_lift_link");
+  if (with_torso)
+  {
+    c.base_pose[3] = 0.0;
+    c.base_pose[11] = 0.051;  // base_link
+  }
+  g.link_names.push_back(with_torso ? "base_link" : "torso_lift_link");
   int dof = 0, k = 1;
   for (const bool left : arms_left)
   {
     std::vector<JointRow> rows;
+    if (with_torso)
+      rows.push_back({ "torso_lift_joint", "torso_lift_link", THIP_JOINT_PRISMATIC, { -0.05, 0.0, 0.739675 },
+                       { 0, 0, 1 }, 0.0, 0.33 });
     armRows(left, rows);
     int prev = 0;  // each arm hangs off the root
     for (const auto& r : rows)
@@ -112,7 +122,8 @@ KinematicGroup makeGroup(const std::string& name, const std::vector<bool>& arms_
     bf[static_cast<std::size_t>(i)] = bl[static_cast<std::size_t>(i)] = eye[i];
   bl[11] = 0.051;
   g.static_frames["base_footprint"] = bf;
-  g.static_frames["base_link"] = bl;
+  if (!with_torso)
+    g.static_frames["base_link"] = bl;
   return g;
 }
 }  // namespace
@@ -125,6 +136,8 @@ Environment::Ptr Environment::makePR2()
   env->addJointGroup(makeGroup("right_arm", { false }));
   env->addJointGroup(makeGroup("left_arm", { true }));
   env->addJointGroup(makeGroup("both_arms", { true, false }));
+  // the torso joint and the right arm (8 joints of pr2.srdf's full_body group, :51-70)
+  env->addJointGroup(makeGroup("torso_right_arm", { false }, true));
   // 2 spheres per moving arm link (link, center in the link frame, radius),
   // trajopt_amd/scene.py PR2_ARM_SPHERES; the left arm mirrors the right
   const char* links[] = { "shoulder_pan_link", "shoulder_pan_link", "shoulder_lift_link", "shoulder_lift_link",

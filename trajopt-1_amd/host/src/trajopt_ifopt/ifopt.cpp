@@ -87,6 +87,7 @@ std::shared_ptr<const Var> Node::addVar(const std::string& name, const std::vect
                                         const VectorXd& values, const std::vector<Bounds>& bounds)
 {
   vars_.push_back(std::make_shared<Var>(name, child_names, values, bounds));
+  vars_.back()->parent_ = this;
   return vars_.back();
 }
 
@@ -94,12 +95,15 @@ NodesVariables::NodesVariables(std::string name, std::vector<std::unique_ptr<Nod
   : name_(std::move(name)), nodes_(std::move(nodes))
 {
   for (const auto& n : nodes_)
+  {
+    n->parent_ = this;
     for (const auto& v : n->getVars())
     {
       v->index_ = rows_;
       rows_ += v->size();
       vars_.push_back(v);
     }
+  }
   setVariables(getValues());
 }
 

@@ -1,0 +1,259 @@
+// Stand-alone driver over the trajopt_ifopt kinematic sets and the collision-set
+// C-ABI (not part of libtrajopt_host), built with AddressSanitizer + UBSan
+// (make -C trajopt-1_amd/host san-ifoptsets; coll_sets.hip's host code is
+// compiled into it with the same sanitizers): the constructors' validation of
+// CartPosConstraint, SingleTimestepCollisionEvaluator and
+// DiscreteCollisionConstraint, the RangeBoundHandling split, and
+// thip_csets_create's validation with out-of-range steps and max_num_cnt, a
+// non-finite margin and an inverted range, at the ends of int's range.  Every
+// refusal must carry its message and come before any device call, so no GPU is
+// needed; the sanitizers turn memory errors and signed overflow into a non-zero
+// exit.
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <exception>
+#include <functional>
+#include <limits>
+#include <memory>
+#include <string>
+
+#include "trajopt_ifopt/constraints/cartesian_position_constraint.h"
+#include "trajopt_ifopt/constraints/collision/discrete_collision_constraint.h"
+
+namespace
+{
+using namespace trajopt_ifopt;
+int g_failures = 0;
+
+void expect(bool ok, const std::string& what)
+{
+  if (!ok)
+  {
+    std::fprintf(stderr, "FAIL: %s\n", what.c_str());
+    ++g_failures;
+  }
+}
+
+void refused(const std::function<void()>& f, const char* needle)
+{
+  try
+  {
+    f();
+    expect(false, std::string("accepted, expected '") + needle + "'");
+  }
+  catch (const std::exception& e)
+  {
+    expect(std::strstr(e.what(), needle) != nullptr, std::string("message '") + e.what() + "' lacks '" + needle + "'");
+  }
+}
+
+struct Vars
+{
+  std::shared_ptr<NodesVariables> variables;
+  std::vector<std::shared_ptr<const Var>> vars;
+};
+
+Vars makeVars(int n_nodes, int n_dof)
+{
+  Vars v;
+  std::vector<std::unique_ptr<Node>> nodes;
+  for (int t = 0; t < n_nodes; ++t)
+  {
+    auto node = std::make_unique<Node>("Joint_Position_" + std::to_string(t));
+    v.vars.push_back(node->addVar("position", std::vector<std::string>(static_cast<std::size_t>(n_dof), "j"),
+                                  VectorXd(static_cast<std::size_t>(n_dof), 0.0),
+                                  std::vector<Bounds>(static_cast<std::size_t>(n_dof), NoBound)));
+    nodes.push_back(std::move(node));
+  }
+  v.variables = std::make_shared<NodesVariables>("joint_trajectory", std::move(nodes));
+  return v;
+}
+
+void csetsRefused(const thip_problem_desc& d, thip_csets_config cfg, const char* needle)
+{
+  thip_csets* cs = nullptr;
+  const int rc = thip_csets_create(0, &d, &cfg, 1, &cs);
+  const std::string msg = thip_csets_last_error(nullptr);
+  expect(rc == THIP_E_INVALID && cs == nullptr, std::string("thip_csets_create accepted, expected '") + needle + "'");
+  expect(msg.find(needle) != std::string::npos, "message '" + msg + "' lacks '" + needle + "'");
+}
+}  // namespace
+
+int main()
+{
+  const auto env = trajopt::Environment::builtin("right_arm");
+  const auto kin = env->getJointGroup("right_arm");
+  const std::string tool = "r_gripper_tool_frame", root = "base_footprint";
+  const double inf = std::numeric_limits<double>::infinity();
+
+  // ---- CartPosConstraint
+  {
+    Vars v = makeVars(2, 7);
+    const VectorXd ones(6, 1.0);
+    const std::vector<Bounds> zero(6, BoundZero);
+    refused([&] { CartPosConstraint(v.vars[0], kin, "r_gripper", root); },
+            "Source Link name 'r_gripper' provided does not exist.");
+    refused([&] { CartPosConstraint(v.vars[0], kin, tool, "table"); }, "Target Link name 'table' provided does not exist.");
+    refused([&] { CartPosConstraint(v.vars[0], ones, std::vector<Bounds>(5, BoundZero), kin, tool, root); },
+            "The number of bounds should be six.");
+    refused([&] { CartPosConstraint(v.vars[0], VectorXd(7, 1.0), zero, kin, tool, root); },
+            "The number of coeffs should be six.");
+    refused([&] { CartPosConstraint(v.vars[0], VectorXd(), zero, kin, tool, root); }, "The number of coeffs should be six.");
+    refused([&] { CartPosConstraint(v.vars[0], kin, "base_link", root); },
+            "CartPosInfo: Target and Source are both static links.");
+    refused([&] { CartPosConstraint(v.vars[0], kin, tool, "r_elbow_flex_link"); }, "kBothActive");
+    refused([&] { CartPosConstraint(nullptr, kin, tool, root); }, "null position variable");
+    // a Var that is in no NodesVariables
+    {
+      Node loose("loose");
+      auto lv = loose.addVar("position", std::vector<std::string>(7, "j"), VectorXd(7, 0.0), std::vector<Bounds>(7, NoBound));
+      refused([&] { CartPosConstraint(lv, kin, tool, root); }, "is in no NodesVariables yet");
+    }
+    // a Var of another size
+    {
+      Vars w = makeVars(1, 5);
+      refused([&] { CartPosConstraint(w.vars[0], kin, tool, root); }, "the group 7 joints");
+    }
+    // the default set: ones and BoundZero, six rows
+    {
+      CartPosConstraint c(v.vars[0], kin, tool, root);
+      expect(c.getRows() == 6 && c.getBounds().size() == 6 && c.getCoefficients() == ones, "default set");
+      expect(c.getType() == CartPosConstraint::Type::kSourceActive, "source active");
+      c.use_numeric_differentiation = false;
+      refused([&] { c.getJacobian(); }, "use_numeric_differentiation = false");
+      refused([&] { c.update(); }, "use_numeric_differentiation = false");
+      const Pose12 p = c.getCurrentPose();
+      expect(std::isfinite(p[3]) && std::fabs(p[0] * p[0] + p[4] * p[4] + p[8] * p[8] - 1.0) < 1e-12, "current pose");
+      Pose12 t = poseIdentity();
+      t[3] = 0.5;
+      c.setTargetPose(t);
+      expect(c.getTargetPose() == t, "setTargetPose");
+    }
+    // the split: a zero coefficient drops its row, a range bound becomes two rows
+    {
+      const VectorXd co{ 1, 5, 0, 2, 2, 2 };
+      const std::vector<Bounds> b{ BoundZero, Bounds(-0.1, 0.2), Bounds(-9, 9), BoundZero, Bounds(0.25, inf), BoundZero };
+      CartPosConstraint c(v.vars[1], co, b, kin, root, tool);  // target active
+      expect(c.getType() == CartPosConstraint::Type::kTargetActive, "target active");
+      expect(c.getRows() == 6 && c.getIndices() == std::vector<int>({ 0, 1, 1, 3, 4, 5 }), "split rows");
+      expect(c.getCoefficients() == VectorXd({ 1, 5, 5, 2, 2, 2 }), "split coefficients");
+      const auto bb = c.getBounds();
+      expect(bb[1].getLower() == -0.1 && bb[1].getUpper() == inf && bb[2].getLower() == -inf && bb[2].getUpper() == 0.2,
+             "split bounds");
+      CartPosConstraint k(v.vars[1], co, b, kin, root, tool, poseIdentity(), poseIdentity(), "keep",
+                          RangeBoundHandling::kKeepAsIs);
+      expect(k.getRows() == 5 && k.getBounds()[1].getType() == BoundsType::kRangeBound, "kKeepAsIs");
+    }
+  }
+
+  // ---- the collision evaluator and the fixed-size set
+  {
+    Vars v = makeVars(3, 7);
+    trajopt_common::TrajOptCollisionConfig cfg(0.1, 1.0);
+    trajopt_common::TrajOptCollisionConfig lvs(0.1, 1.0, trajopt_common::CollisionEvaluatorType::LVS_DISCRETE);
+    refused([&] { SingleTimestepCollisionEvaluator(kin, env, lvs); },
+            "SingleTimestepCollisionEvaluator, should be configured with DISCRETE");
+    auto bare = std::make_shared<trajopt::Environment>();
+    bare->addJointGroup(*kin);
+    refused([&] { SingleTimestepCollisionEvaluator(bare->getJointGroup("right_arm"), bare, cfg); },
+            "sphere model is missing");
+    refused([&] { SingleTimestepCollisionEvaluator(nullptr, env, cfg); }, "null kinematic group");
+    auto ev = std::make_shared<SingleTimestepCollisionEvaluator>(kin, env, cfg);
+    expect(ev->getCollisionMarginBuffer() == 0.01, "default buffer");
+    refused([&] { DiscreteCollisionConstraint(ev, v.vars[0], 0); }, "max_num_cnt must be greater than zero!");
+    refused([&] { DiscreteCollisionConstraint(ev, v.vars[0], INT_MIN); }, "max_num_cnt must be greater than zero!");
+    refused([&] { DiscreteCollisionConstraint(ev, v.vars[0], INT_MAX); }, "rows per node");
+    refused([&] { DiscreteCollisionConstraint(nullptr, v.vars[0], 1); }, "null position variable or evaluator");
+    {
+      Vars w = makeVars(1, 2);
+      refused([&] { DiscreteCollisionConstraint(ev, w.vars[0], 1); }, "the group 7 joints");
+    }
+    DiscreteCollisionConstraint c(ev, v.vars[1], 3, true);
+    expect(c.getRows() == 3 && c.getCoefficients() == VectorXd(3, 1.0), "three rows of ones");
+    expect(c.getBounds()[2].getType() == BoundsType::kUpperBound && c.getBounds()[2].getUpper() == 0.0, "BoundSmallerZero");
+    refused([&] { c.setBounds(std::vector<Bounds>(2, BoundZero)); }, "2 bounds for 3 rows");
+    c.setBounds(std::vector<Bounds>(3, Bounds(-inf, -0.01)));
+    expect(c.getBounds()[0].getUpper() == -0.01, "setBounds");
+    {
+      Vars w = makeVars(1, 7);  // another variable set on the same evaluator
+      refused([&] { DiscreteCollisionConstraint(ev, w.vars[0], 1); }, "must share one NodesVariables");
+    }
+    // a Var between two registered ones that was never registered is refused, before any device call
+    {
+      auto ev2 = std::make_shared<SingleTimestepCollisionEvaluator>(kin, env, cfg);
+      DiscreteCollisionConstraint a(ev2, v.vars[0], 1), b(ev2, v.vars[2], 1);
+      refused([&] { ev2->rows(*v.vars[1]); }, "was not registered");
+    }
+    // the descriptor the evaluator hands to thip_csets_create, with a pair entry
+    trajopt_common::TrajOptCollisionConfig pc(0.1, 1.0);
+    pc.setPairData("r_wrist_roll_link", "r_shoulder_pan_link", 0.05, 0.0);
+    pc.setPairData("nobody", "r_shoulder_pan_link", 0.05, 3.0);  // names no pair: dropped
+    SingleTimestepCollisionEvaluator pe(kin, env, pc);
+    auto d = std::make_unique<thip_problem_desc>();
+    std::vector<double> scene;
+    pe.lower(*d, scene);
+    expect(d->n_spheres == 14 && d->n_self_pairs == 2 && d->n_coll_pairs == 1 && d->coll_pairs[0].other < 0, "lowered");
+
+    // ---- thip_csets_create: every refusal before any device call
+    d->n_steps = 3;
+    thip_csets_config good{ 0.1, 1.0, 0.01, 3, 0, 2 };
+    auto with = [&](std::function<void(thip_csets_config&)> f) {
+      thip_csets_config c2 = good;
+      f(c2);
+      return c2;
+    };
+    csetsRefused(*d, with([](auto& c2) { c2.max_num_cnt = 0; }), "max_num_cnt 0 out of range");
+    csetsRefused(*d, with([](auto& c2) { c2.max_num_cnt = THIP_CSETS_MAX_ROWS + 1; }), "max_num_cnt 65 out of range");
+    csetsRefused(*d, with([](auto& c2) { c2.max_num_cnt = INT_MAX; }), "out of range");
+    csetsRefused(*d, with([](auto& c2) { c2.max_num_cnt = INT_MIN; }), "out of range");
+    csetsRefused(*d, with([](auto& c2) { c2.first_step = -1; }), "outside [0, 2]");
+    csetsRefused(*d, with([](auto& c2) { c2.last_step = 3; }), "outside [0, 2]");
+    csetsRefused(*d, with([](auto& c2) { c2.first_step = INT_MIN, c2.last_step = INT_MAX; }), "outside [0, 2]");
+    csetsRefused(*d, with([](auto& c2) { c2.first_step = INT_MAX, c2.last_step = INT_MIN; }), "outside [0, 2]");
+    csetsRefused(*d, with([](auto& c2) { c2.last_step = INT_MAX; }), "outside [0, 2]");
+    csetsRefused(*d, with([](auto& c2) { c2.first_step = 2, c2.last_step = 1; }), "inverted step range [2, 1]");
+    csetsRefused(*d, with([](auto& c2) { c2.margin = std::nan(""); }), "margin is not finite");
+    csetsRefused(*d, with([=](auto& c2) { c2.margin = -inf; }), "margin is not finite");
+    csetsRefused(*d, with([=](auto& c2) { c2.coeff = inf; }), "coeff is not finite");
+    csetsRefused(*d, with([](auto& c2) { c2.margin_buffer = std::nan(""); }), "margin_buffer is not finite");
+    {
+      auto e = std::make_unique<thip_problem_desc>(*d);
+      e->n_spheres = 0;
+      csetsRefused(*e, good, "no robot spheres");
+      *e = *d;
+      e->n_steps = INT_MAX;
+      csetsRefused(*e, good, "n_steps out of range");
+      *e = *d;
+      e->n_prims = INT_MIN;
+      csetsRefused(*e, good, "n_prims out of range");
+      *e = *d;
+      e->coll_pairs[0].other = INT_MIN;
+      csetsRefused(*e, good, "coll_pairs[0].other out of range");
+      *e = *d;
+      e->coll_pairs[0].link = INT_MAX;
+      csetsRefused(*e, good, "coll_pairs[0].link out of range");
+      *e = *d;
+      e->sphere_link[0] = INT_MAX;
+      csetsRefused(*e, good, "bad sphere link");
+      *e = *d;
+      e->n_self_pairs = INT_MAX;
+      csetsRefused(*e, good, "n_self_pairs out of range");
+      // a link pair listed twice, as given and reversed: the selection's keys must be unique
+      *e = *d;
+      e->self_pair[1][0] = e->self_pair[0][0];
+      e->self_pair[1][1] = e->self_pair[0][1];
+      csetsRefused(*e, good, "self_pair[1] repeats self_pair[0]");
+      *e = *d;
+      e->self_pair[1][0] = e->self_pair[0][1];
+      e->self_pair[1][1] = e->self_pair[0][0];
+      csetsRefused(*e, good, "self_pair[1] repeats self_pair[0]");
+    }
+    thip_csets* cs = nullptr;
+    expect(thip_csets_create(0, d.get(), &good, INT_MIN, &cs) == THIP_E_INVALID, "batch");
+    expect(thip_csets_create(0, nullptr, &good, 1, &cs) == THIP_E_INVALID, "null descriptor");
+  }
+  std::printf("ifopt_sets_san: %d failures\n", g_failures);
+  return g_failures ? 1 : 0;
+}

@@ -298,6 +298,22 @@ class CheckResult(C.Structure):
     ]
 
 
+CSETS_MAX_ROWS = 64  # THIP_CSETS_MAX_ROWS: rows per node of a collision set
+
+
+class CsetsConfig(C.Structure):
+    """thip_csets_config: the collision sets of thip_csets_* (TrajOptCollisionConfig's
+    margin / coeff / buffer, rows per node, the nodes that carry a set)."""
+    _fields_ = [
+        ("margin", C.c_double),
+        ("coeff", C.c_double),
+        ("margin_buffer", C.c_double),
+        ("max_num_cnt", C.c_int),
+        ("first_step", C.c_int),
+        ("last_step", C.c_int),
+    ]
+
+
 TERM_JOINT_VEL, TERM_JVX, TERM_JPOS, TERM_JDT, TERM_CART, TERM_COLL = range(6)  # thip_term_slot.kind (THIP_TERM_*)
 TERM_KIND_NAMES = ("joint_vel", "jvx", "jpos", "jdt", "cart", "coll")
 # workspace arrays of layout.hpp's DArr / IArr that thip_debug_layout + thip_debug_workspace expose to tests
@@ -493,6 +509,29 @@ def _declare(lib):
     lib.thip_terms_destroy.restype = None
     lib.thip_terms_last_error.argtypes = [vp]
     lib.thip_terms_last_error.restype = C.c_char_p
+    ip = P(C.c_int)
+    lib.thip_default_csets_config.argtypes = [P(CsetsConfig)]
+    lib.thip_default_csets_config.restype = None
+    lib.thip_sizeof_csets_config.argtypes = []
+    lib.thip_sizeof_csets_config.restype = C.c_int
+    lib.thip_csets_create.argtypes = [C.c_int, P(ProblemDesc), P(CsetsConfig), C.c_int, P(vp)]
+    lib.thip_csets_create.restype = C.c_int
+    lib.thip_csets_upload.argtypes = [vp, dp]
+    lib.thip_csets_upload.restype = C.c_int
+    lib.thip_csets_upload_device.argtypes = [vp, vp]
+    lib.thip_csets_upload_device.restype = C.c_int
+    lib.thip_csets_nodes.argtypes = [vp]
+    lib.thip_csets_nodes.restype = C.c_int
+    lib.thip_csets_run.argtypes = [vp, dp, dp, dp, dp, ip, ip]
+    lib.thip_csets_run.restype = C.c_int
+    lib.thip_csets_run_device.argtypes = [vp, vp, dp, dp, dp, ip, ip]
+    lib.thip_csets_run_device.restype = C.c_int
+    lib.thip_csets_last_ms.argtypes = [vp]
+    lib.thip_csets_last_ms.restype = C.c_double
+    lib.thip_csets_destroy.argtypes = [vp]
+    lib.thip_csets_destroy.restype = None
+    lib.thip_csets_last_error.argtypes = [vp]
+    lib.thip_csets_last_error.restype = C.c_char_p
     lib.thip_debug_layout.argtypes = [vp, P(C.c_longlong), P(C.c_longlong), P(C.c_longlong)]
     lib.thip_debug_layout.restype = C.c_int
     lib.thip_debug_workspace.argtypes = [vp, dp, P(C.c_int)]
@@ -529,6 +568,8 @@ def load_hip():
             raise RuntimeError("thip_check_config / thip_check_result layout mismatch between Python and the HIP library")
         if _hip.thip_sizeof_term_slot() != C.sizeof(TermSlot):
             raise RuntimeError("thip_term_slot layout mismatch between Python and the HIP library")
+        if _hip.thip_sizeof_csets_config() != C.sizeof(CsetsConfig):
+            raise RuntimeError("thip_csets_config layout mismatch between Python and the HIP library")
     return _hip
 
 

@@ -404,3 +404,74 @@ class TrajectoryChecker:
             self.close()
         except Exception:
             pass
+
+
+class CollisionSets:
+    """thip_csets_*: the rows of trajopt_ifopt's fixed-size DiscreteCollisionConstraint
+    (SingleTimestepCollisionEvaluator) at every node of [first_step, last_step]
+    of every problem, one launch per x.  Reads the chain, robot spheres,
+    self-collision pairs, n_prims, n_steps and collision term 0's coll_pairs of
+    `desc`; config: abi.CsetsConfig; scene [B, n_prims, 16]."""
+
+    def __init__(self, desc, batch, scene, config, device: int = 0):
+        self.lib = abi.load_hip()
+        self.batch = batch
+        self.n_steps, self.n_dof = desc.n_steps, desc.chain.n_dof
+        self.config = config
+        self.cs = C.c_void_p()
+        rc = self.lib.thip_csets_create(device, C.byref(desc), C.byref(config), batch, C.byref(self.cs))
+        if rc != 0:
+            raise HipError(f"thip_csets_create: {self.lib.thip_csets_last_error(None).decode()}")
+        self.n_nodes = self.lib.thip_csets_nodes(self.cs)
+        self.rows = config.max_num_cnt
+        self._scene = np.ascontiguousarray(scene, dtype=np.float64) if desc.n_prims > 0 else None
+        if self._scene is not None and self._scene.size != batch * desc.n_prims * 16:
+            self.close()
+            raise HipError(f"CollisionSets: scene has {self._scene.size} values, not [batch][n_prims][16]")
+        self._check(self.lib.thip_csets_upload(self.cs, None if self._scene is None else _dp(self._scene)),
+                    "thip_csets_upload")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise HipError(f"{what}: {self.lib.thip_csets_last_error(self.cs).decode()}")
+
+    def _out(self):
+        B, n, R = self.batch, self.n_nodes, self.rows
+        return (np.zeros((B, n, R)), np.zeros((B, n, R, self.n_dof)), np.zeros((B, n, R)),
+                np.zeros((B, n), dtype=np.int32), np.zeros((B, n, R, 4), dtype=np.int32))
+
+    @staticmethod
+    def _ip(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int))
+
+    def run(self, x):
+        """x [B, N, D] (host) -> values [B, n, R], jac [B, n, R, D], coeffs [B, n, R],
+        counts [B, n], keys [B, n, R, 4] (link, other, sphere, other_sphere)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != self.batch * self.n_steps * self.n_dof:
+            raise HipError(f"CollisionSets.run: x has {x.size} values, not [batch][n_steps][n_dof]")
+        v, J, cf, cnt, keys = self._out()
+        self._check(self.lib.thip_csets_run(self.cs, _dp(x), _dp(v), _dp(J), _dp(cf), self._ip(cnt), self._ip(keys)),
+                    "thip_csets_run")
+        return v, J, cf, cnt, keys
+
+    def run_device(self, d_x):
+        """As run() on trajectories already on the device (an address)."""
+        v, J, cf, cnt, keys = self._out()
+        self._check(self.lib.thip_csets_run_device(self.cs, C.c_void_p(d_x), _dp(v), _dp(J), _dp(cf), self._ip(cnt),
+                                                   self._ip(keys)), "thip_csets_run_device")
+        return v, J, cf, cnt, keys
+
+    def kernel_ms(self) -> float:
+        return float(self.lib.thip_csets_last_ms(self.cs))
+
+    def close(self):
+        if self.cs:
+            self.lib.thip_csets_destroy(self.cs)
+            self.cs = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

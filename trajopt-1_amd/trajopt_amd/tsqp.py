@@ -7,6 +7,10 @@ the QP lives in thip_qp's resident GPU workspace (trajopt_sqp::GpuQPSolver).
 `Spec` mirrors tsqp_spec: a joint trajectory of n_nodes nodes with joint
 position / velocity / acceleration / jerk terms, as constraints or as squared /
 absolute / hinge costs.  `solve` runs the C++ product path on a HIP device.
+`KinSpec` mirrors tsqp_kin_spec: CartPosConstraint sets and fixed-size
+DiscreteCollisionConstraint sets on the built-in environment of a group, their
+values and jacobians from the device; `solve_kin` solves with them, `eval_kin`
+returns every set's values, jacobian, coefficients and bounds without a solve.
 """
 from __future__ import annotations
 
@@ -51,9 +55,45 @@ class Result(C.Structure):
                 ("admm_iters", C.c_longlong), ("best_exact_merit", C.c_double)]
 
 
+KIN_MAX_CART, KIN_MAX_COLL, KIN_MAX_PRIMS, KIN_NAME_LEN = 16, 4, 32, 64
+IDENTITY12 = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+class CartTerm(C.Structure):
+    _fields_ = [("node", C.c_int), ("penalty", C.c_int), ("analytic_jacobian", C.c_int), ("pad_", C.c_int),
+                ("source_frame", C.c_char * KIN_NAME_LEN),
+                ("target_frame", C.c_char * KIN_NAME_LEN), ("source_offset", C.c_double * 12),
+                ("target_offset", C.c_double * 12), ("coeffs", C.c_double * 6), ("lower", C.c_double * 6),
+                ("upper", C.c_double * 6)]
+
+
+class CollTerm(C.Structure):
+    _fields_ = [("first", C.c_int), ("last", C.c_int), ("penalty", C.c_int), ("max_num_cnt", C.c_int),
+                ("fixed_sparsity", C.c_int), ("margin", C.c_double), ("coeff", C.c_double), ("buffer", C.c_double)]
+
+
+class KinSpec(C.Structure):
+    _fields_ = [("manip", C.c_char * KIN_NAME_LEN), ("n_prims", C.c_int),
+                ("prims", (C.c_double * 16) * KIN_MAX_PRIMS), ("n_cart", C.c_int), ("cart", CartTerm * KIN_MAX_CART),
+                ("n_coll", C.c_int), ("coll", CollTerm * KIN_MAX_COLL)]
+
+
 def _lib():
     L = host.load_host()
     if not hasattr(L, "_tsqp_ready"):
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        L.thost_tsqp_solve_kin.argtypes = [C.POINTER(Spec), C.POINTER(KinSpec), C.c_int, dp, C.POINTER(Result),
+                                           C.c_char_p, C.c_int]
+        L.thost_tsqp_solve_kin.restype = C.c_int
+        L.thost_tsqp_eval_kin.argtypes = [C.POINTER(Spec), C.POINTER(KinSpec), C.c_int, dp, C.c_int, ip, ip, C.c_int,
+                                          dp, dp, dp, dp, dp, C.c_int, dp, dp, C.POINTER(C.c_longlong), C.c_char_p,
+                                          C.c_int]
+        L.thost_tsqp_eval_kin.restype = C.c_int
+        for fn, st in (("thost_tsqp_sizeof_kin_spec", KinSpec), ("thost_tsqp_sizeof_cart_term", CartTerm),
+                       ("thost_tsqp_sizeof_coll_term", CollTerm)):
+            getattr(L, fn).restype = C.c_int
+            if getattr(L, fn)() != C.sizeof(st):
+                raise RuntimeError(f"{st.__name__} layout mismatch between Python and the host library")
         L.thost_tsqp_defaults.argtypes = [C.POINTER(Spec)]
         L.thost_tsqp_defaults.restype = None
         L.thost_tsqp_solve.argtypes = [C.POINTER(Spec), C.c_int, C.POINTER(C.c_double), C.POINTER(Result),
@@ -122,3 +162,94 @@ def solve(spec: Spec, device: int = 0):
     if rc != 0:
         raise host.HostError(err.value.decode())
     return x, res
+
+
+def make_kin_spec(manip, cart=(), coll=(), prims=None):
+    """manip: a group of the built-in environments ("right_arm", "left_arm",
+    "both_arms", spherebot's "manipulator").  cart: dicts with node, source_frame,
+    target_frame, source_offset / target_offset (12 values, default identity),
+    coeffs (6, default ones), lower / upper (6, default zeros: BoundZero), penalty,
+    analytic_jacobian (use_numeric_differentiation = false: refused).
+    coll: dicts with first, last (default first), margin, coeff, buffer,
+    max_num_cnt, fixed_sparsity, penalty.  prims [n, 16]: scene primitives added
+    to the environment's own."""
+    if len(cart) > KIN_MAX_CART or len(coll) > KIN_MAX_COLL:
+        raise ValueError("kinematic spec exceeds TSQP_KIN_MAX_CART / TSQP_KIN_MAX_COLL")
+    k = KinSpec()
+    k.manip = manip.encode()
+    prims = np.zeros((0, 16)) if prims is None else np.asarray(prims, dtype=np.float64).reshape(-1, 16)
+    if len(prims) > KIN_MAX_PRIMS:
+        raise ValueError("kinematic spec exceeds TSQP_KIN_MAX_PRIMS")
+    k.n_prims = len(prims)
+    for p, rec in enumerate(prims):
+        for i in range(16):
+            k.prims[p][i] = float(rec[i])
+    k.n_cart = len(cart)
+    for i, t in enumerate(cart):
+        T = k.cart[i]
+        T.node, T.penalty = int(t.get("node", 0)), int(t.get("penalty", CONSTRAINT))
+        T.analytic_jacobian = int(bool(t.get("analytic_jacobian", False)))
+        T.source_frame, T.target_frame = t["source_frame"].encode(), t["target_frame"].encode()
+        so = np.asarray(t.get("source_offset", IDENTITY12), dtype=np.float64).reshape(12)
+        to = np.asarray(t.get("target_offset", IDENTITY12), dtype=np.float64).reshape(12)
+        co, lo = list(t.get("coeffs", [1.0] * 6)), list(t.get("lower", [0.0] * 6))
+        up = list(t.get("upper", lo))
+        if len(co) != 6 or len(lo) != 6 or len(up) != 6:
+            raise ValueError("a CartPos term takes 6 coefficients and 6 bounds")
+        for j in range(12):
+            T.source_offset[j], T.target_offset[j] = float(so[j]), float(to[j])
+        for j in range(6):
+            T.coeffs[j], T.lower[j], T.upper[j] = float(co[j]), float(lo[j]), float(up[j])
+    k.n_coll = len(coll)
+    for i, t in enumerate(coll):
+        T = k.coll[i]
+        T.first = int(t.get("first", 0))
+        T.last = int(t.get("last", T.first))
+        T.penalty = int(t.get("penalty", CONSTRAINT))
+        T.max_num_cnt, T.fixed_sparsity = int(t.get("max_num_cnt", 3)), int(bool(t.get("fixed_sparsity", True)))
+        T.margin, T.coeff, T.buffer = float(t["margin"]), float(t.get("coeff", 1.0)), float(t.get("buffer", 0.01))
+    return k
+
+
+def solve_kin(spec: Spec, kin: KinSpec, device: int = 0):
+    """solve() with the kinematic sets of `kin` added (thost_tsqp_solve_kin)."""
+    L = _lib()
+    x = np.zeros((spec.n_nodes, spec.n_dof))
+    res = Result()
+    err = C.create_string_buffer(4096)
+    if L.thost_tsqp_solve_kin(C.byref(spec), C.byref(kin), device, x.ctypes.data_as(C.POINTER(C.c_double)),
+                              C.byref(res), err, 4096) != 0:
+        raise host.HostError(err.value.decode())
+    return x, res
+
+
+def eval_kin(spec: Spec, kin: KinSpec, xs, probe_q=None, device: int = 0, cap_sets=256, cap_rows=2048):
+    """Every set of (spec, kin) at each variable vector of xs [n_x, n_nodes, n_dof],
+    without a solve (thost_tsqp_eval_kin) -> dict: set_rows [n_sets]; values,
+    coeffs [n_x, rows]; jac [n_x, rows, n_nodes * n_dof]; lower, upper [rows];
+    launches (CartPos evaluator, collision evaluators); probe [rows] with every
+    CartPos set's calcValues(probe_q) in its rows (NaN elsewhere) when probe_q is given."""
+    L = _lib()
+    dp = C.POINTER(C.c_double)
+    xs = np.ascontiguousarray(xs, dtype=np.float64).reshape(-1, spec.n_nodes, spec.n_dof)
+    n_x, nv = len(xs), spec.n_nodes * spec.n_dof
+    n_sets = C.c_int(0)
+    set_rows = np.zeros(cap_sets, dtype=np.int32)
+    values, coeffs = np.zeros((n_x, cap_rows)), np.zeros((n_x, cap_rows))
+    jac = np.zeros((n_x, cap_rows, nv))
+    lower, upper = np.zeros(cap_rows), np.zeros(cap_rows)
+    probe = np.full(cap_rows, np.nan)
+    pq = None if probe_q is None else np.ascontiguousarray(probe_q, dtype=np.float64)
+    launches = (C.c_longlong * 2)()
+    err = C.create_string_buffer(4096)
+    d = lambda a: a.ctypes.data_as(dp)  # noqa: E731
+    rc = L.thost_tsqp_eval_kin(C.byref(spec), C.byref(kin), device, d(xs), n_x, C.byref(n_sets),
+                               set_rows.ctypes.data_as(C.POINTER(C.c_int)), cap_sets, d(values), d(jac), d(coeffs),
+                               d(lower), d(upper), cap_rows, None if pq is None else d(pq), d(probe), launches, err,
+                               4096)
+    if rc != 0:
+        raise host.HostError(err.value.decode())
+    rows = int(set_rows[:n_sets.value].sum())
+    return {"set_rows": set_rows[:n_sets.value].copy(), "values": values[:, :rows], "coeffs": coeffs[:, :rows],
+            "jac": jac[:, :rows], "lower": lower[:rows], "upper": upper[:rows], "probe": probe[:rows],
+            "launches": (int(launches[0]), int(launches[1]))}
