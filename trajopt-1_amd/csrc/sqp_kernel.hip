@@ -4995,20 +4995,31 @@ __device__ int admm_segment(Ctx& c, Solver& sv, int it, int stop, int interval, 
   auto hinge_gather_seg = [&](auto HTP) {
     const int k = tid & 15;
     if (k < 2 * D)
-#pragma unroll 2
       for (int q = tid >> 4; q < nchk; q += kBlock / 16)
       {
         const int h0 = CHKl[2 * q], h1 = CHKl[2 * q + 1];
+        // the chunk's coefficients and multipliers, all in flight before the
+        // first wait: without the scheduling barrier the loads are issued in
+        // groups, each drained before the next (one wave per SIMD: every
+        // drain is exposed latency).  One chunk at a time: the barrier keeps
+        // the loop from being unrolled, and two chunks in flight by hand put
+        // scratch reloads into the iteration loop
+        double ca[kHChunk], cm[kHChunk];
+#pragma unroll
+        for (int i = 0; i < kHChunk; ++i)
+        {
+          const int hi = min(h0 + i, h1 - 1);  // in bounds
+          ca[i] = HTP[k * nhs + hi];
+          cm[i] = MRl[nr + hi];
+        }
+        __builtin_amdgcn_sched_barrier(0);
         double s0 = 0, s1 = 0;
 #pragma unroll
         for (int i = 0; i < kHChunk; i += 2)
         {
-          const int ha = min(h0 + i, h1 - 1), hb = min(h0 + i + 1, h1 - 1);  // in bounds
-          const double aa = HTP[k * nhs + ha], ma = MRl[nr + ha];
-          const double ab = HTP[k * nhs + hb], mb2 = MRl[nr + hb];
           // masked by 0/1 multipliers, not selects (see masked_dot)
-          s0 += aa * (ma * ((h0 + i < h1) ? 1.0 : 0.0));
-          s1 += ab * (mb2 * ((h0 + i + 1 < h1) ? 1.0 : 0.0));
+          s0 += ca[i] * (cm[i] * ((h0 + i < h1) ? 1.0 : 0.0));
+          s1 += ca[i + 1] * (cm[i + 1] * ((h0 + i + 1 < h1) ? 1.0 : 0.0));
         }
         PARTlw[q * 16 + k] = s0 + s1;
       }
@@ -5024,27 +5035,48 @@ __device__ int admm_segment(Ctx& c, Solver& sv, int it, int stop, int interval, 
   auto hinge_e = [&](auto PKP, auto HTP, bool last) {
     for (int h = tid; h < nh; h += kBlock)
     {
-      // every pack field is read before any store (the stores could alias
-      // them as far as the compiler knows)
+      // Clamped indices (always in bounds), masked accumulation.  The loads
+      // go out in batches, each whole before its first wait (scheduling
+      // barriers: left alone, the scheduler issues them a few at a time and
+      // drains each group): t0 and the coefficients, then the x~ values,
+      // whose addresses need t0.  The other pack fields follow the dot
+      // product: with them in flight as well, 43 doubles, the iteration loop
+      // reloads spilled registers from scratch.
       const int t0 = static_cast<int>(PKP[10 * nh + h]);
-      const double zh = PKP[h], zb = PKP[nh + h], yh = PKP[2 * nh + h], yb = PKP[3 * nh + h];
-      const double xo = PKP[4 * nh + h], uh = PKP[5 * nh + h], dn = PKP[6 * nh + h], w = PKP[7 * nh + h];
-      const double bs = PKP[8 * nh + h], q = PKP[9 * nh + h], deni = PKP[11 * nh + h];
-      const double eta = rho_s * zh - yh;
-      const double rn = (sig * xo - q) + bs * (rho_s * zb - yb);
-      double g0 = 0, g1 = 0;
-      // clamped indices (always in bounds), masked accumulation: the loads
-      // of all terms are in flight together
+      double a0[kOct], a1[kOct], x0[kOct], x1[kOct];
 #pragma unroll
       for (int k = 0; k < kOct; ++k)
       {
         const int kk = (k < D) ? k : D - 1;
-        const double a0 = HTP[kk * nhs + h], a1 = HTP[(D + kk) * nhs + h];
-        const double x0 = lds(CV)[t0 + kk], x1 = lds(CV)[t0 + D + kk];
-        const double mk = (k < D) ? 1.0 : 0.0;  // a 0/1 multiplier, not a select (see masked_dot)
-        g0 += a0 * (x0 * mk);
-        g1 += a1 * (x1 * mk);
+        a0[k] = HTP[kk * nhs + h];
+        a1[k] = HTP[(D + kk) * nhs + h];
       }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < kOct; ++k)
+      {
+        const int kk = (k < D) ? k : D - 1;
+        x0[k] = lds(CV)[t0 + kk];
+        x1[k] = lds(CV)[t0 + D + kk];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      double g0 = 0, g1 = 0;
+#pragma unroll
+      for (int k = 0; k < kOct; ++k)
+      {
+        const double mk = (k < D) ? 1.0 : 0.0;  // a 0/1 multiplier, not a select (see masked_dot)
+        g0 += a0[k] * (x0[k] * mk);
+        g1 += a1[k] * (x1[k] * mk);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // every pack field is read before any store (the stores could alias
+      // them as far as the compiler knows)
+      const double zh = PKP[h], zb = PKP[nh + h], yh = PKP[2 * nh + h], yb = PKP[3 * nh + h];
+      const double xo = PKP[4 * nh + h], uh = PKP[5 * nh + h], dn = PKP[6 * nh + h], w = PKP[7 * nh + h];
+      const double bs = PKP[8 * nh + h], q = PKP[9 * nh + h], deni = PKP[11 * nh + h];
+      __builtin_amdgcn_sched_barrier(0);
+      const double eta = rho_s * zh - yh;
+      const double rn = (sig * xo - q) + bs * (rho_s * zb - yb);
       const double g = g0 + g1;
       const double av = (rn + w * (eta - rho_s * g)) * deni;
       const double zth = g + w * av;
