@@ -594,7 +594,7 @@ int thip_collision_rows(thip_ctx* ctx, const double* x, double* records, int cap
  * the slot list in sqp_kernel.hip).  enable = 0 frees them.  Counters
  * accumulate over runs until re-enabled. */
 int thip_debug_profile(thip_ctx* ctx, int enable);
-int thip_debug_get_profile(thip_ctx* ctx, long long* counters /* [batch][40] */);
+int thip_debug_get_profile(thip_ctx* ctx, long long* counters /* [batch][43] */);
 /* Diagnostics: workspace layout (array offsets in doubles / ints, and
  * dims = {N, D, nx, n_fixed_rows, n_abs, n_cols, n_rows, m, dstride, istride,
  * n_double_arrays, n_int_arrays}) and a copy of the device workspace. */
@@ -626,6 +626,9 @@ int thip_debug_layout(thip_ctx* ctx, long long* doff, long long* ioff, long long
                                          loops over the hinge and CartPose rows and factors the narrow (D <= 8)
                                          diagonal blocks through LDS, as before round 9 (bitwise the same
                                          results) */
+#define THIP_DEBUG_FP_REF 512         /* the SQP driver takes OSQPModel's sparsity fingerprint from thread 0's
+                                         serial walk of A instead of the whole workgroup's (the same decisions,
+                                         so bitwise the same results) */
 int thip_debug_set_path(int flags);
 int thip_debug_workspace(thip_ctx* ctx, double* dws, int* iws);
 /* The solve layout a context chose (diagnostic): out[0] block-solve branches

@@ -263,6 +263,10 @@ struct Layout
   // norms with the serial per-column loops, and factor() / twisted_factor_half
   // run the block Cholesky through LDS with one lane per row (read there only)
   int setup_ref;
+  // diagnostic (THIP_DEBUG_FP_REF): sqp_optimize takes the sparsity fingerprint
+  // from thread 0's serial walk of A (pattern_fingerprint), not from the
+  // workgroup's (pattern_fingerprint_wg); read there only
+  int fp_ref;
 };
 
 // the solve-layout index of column col (t, j): block b * N + t, row j - b sD
@@ -374,6 +378,6 @@ struct KernelArgs
 // bound-row coefficient, q, the first x column, 1 / (DG + rho w^2)
 constexpr int kHPack = 12;
 constexpr int kHChunk = 8;  // hinge rows per gather chunk (rows of one step pair)
-constexpr int kProfSlots = 40;
+constexpr int kProfSlots = 43;
 
 }  // namespace thip

@@ -22,6 +22,7 @@
 #include "collision_device.hpp"
 #include "kin_device.hpp"
 #include "layout.hpp"
+#include "pattern_fp.hpp"
 
 // THIP_GENERIC_ONLY: the generic-step build (layout.hpp kGenBlock threads, no
 // register-resident segment, the fused kernel alone, named sqp_kernel_gen)
@@ -235,7 +236,9 @@ __device__ __forceinline__ const gbl_f64* gbl(const double* p) { return (const g
 // total, 14 sqp total (wall clock, 100 MHz ticks), 15 segment phase B
 // (rhs + Linv b), 16 segment phase C2 (Linv^T y + middle block), 37 segment
 // set-up (entry to the first iteration), 38 segment write-back, 39 segment
-// entries (a count).
+// entries (a count), 40 the sparsity fingerprint with its barriers, 41 the
+// model values at a QP solution, 42 thread 0's merit sums and decision (the
+// SQP driver's own code between its calls).
 struct ProfScope
 {
   long long* p;
@@ -243,6 +246,23 @@ struct ProfScope
   long long t0;
   __device__ ProfScope(const Ctx& c, int s) : p(c.tid == 0 ? c.s->prof : nullptr), slot(s), t0(p ? clock64() : 0) {}
   __device__ ~ProfScope()
+  {
+    if (p)
+      p[slot] += clock64() - t0;
+  }
+};
+// The same for a phase that ends past declarations a scope could not hold
+struct ProfSpan
+{
+  long long* p;
+  long long t0 = 0;
+  __device__ explicit ProfSpan(const Ctx& c) : p(c.tid == 0 ? c.s->prof : nullptr) {}
+  __device__ __forceinline__ void begin()
+  {
+    if (p)
+      t0 = clock64();
+  }
+  __device__ __forceinline__ void end(int slot)
   {
     if (p)
       p[slot] += clock64() - t0;
@@ -6325,6 +6345,120 @@ __device__ void pattern_fingerprint(Ctx& c, unsigned long long& hash, int& n_out
   nnz_out = nnz;
 }
 
+// Thread 0: Ctl::flag = this set-up's (hash, n, m, nnz) equal the previous one's, which they replace
+__device__ __forceinline__ void fingerprint_compare(Ctx& c, unsigned long long fh, int fn, int fm, long long fz)
+{
+  c.s->flag = (fn == c.s->fp_n && fm == c.s->fp_m && fz == c.s->fp_nnz && fh == c.s->fp_hash) ? 1 : 0;
+  c.s->fp_n = fn;
+  c.s->fp_m = fm;
+  c.s->fp_nnz = fz;
+  c.s->fp_hash = fh;
+}
+
+// The same test by the whole workgroup (pattern_fp.hpp): equal (n, m, nnz,
+// hash) for exactly the pairs of set-ups for which the walk above gives equal
+// ones, up to a collision of the 64-bit sums; the hash value itself differs.
+// nnz is a block sum of the masks' popcounts; one thread per x column counts
+// its entries, an exclusive scan of the counts gives every column pointer and
+// every column's first entry number, and each column adds the share of its own
+// pointer and row indices inside the compared prefixes (columns >= nx from
+// closed forms).  The integer tables are read through global-address-space
+// pointers, a group of rows' loads before their first use.  Called by every
+// thread, between the caller's barriers; two barriers inside (one more per
+// further chunk of kBlock x columns); thread 0 compares and stores
+// (fingerprint_compare).  Scratch: Ctl::red as 64-bit words (per wave: 0 popcounts,
+// 1 hash, 2 / 3 scan totals of even / odd column chunks).
+typedef __attribute__((address_space(1))) const int gbl_ci32;
+__device__ __noinline__ void pattern_fingerprint_wg(Ctx& c)
+{
+  const Layout& L = c.L;
+  FpDims d;
+  d.D = L.D;
+  d.N = L.N;
+  d.nx = L.nx;
+  d.nc_base = L.nc_base;
+  d.n_fixed_rows = L.n_fixed_rows;
+  d.n_rows = L.n_rows;
+  d.nh = c.s->n_h;
+  d.hinge = L.hinge;
+  const int nx = L.nx, n = d.n();
+  gbl_ci32 *mask = (gbl_ci32*)c.ia(I_MASK), *HP = (gbl_ci32*)c.ia(I_HPTR), *HM = (gbl_ci32*)c.ia(I_HMASK);
+  gbl_ci32 *fos = (gbl_ci32*)c.T.fixed_of_step, *sp = (gbl_ci32*)c.T.step_ptr, *sr = (gbl_ci32*)c.T.step_rows;
+  unsigned long long* W = reinterpret_cast<unsigned long long*>(c.s->red);
+  static_assert(sizeof(c.s->red[0]) == sizeof(unsigned long long), "Ctl::red as 64-bit words");
+  int bits = 0;
+  FOR(r, L.n_abs) bits += __popc(mask[r]);
+  FOR(h, d.nh) bits += __popc(HM[h]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    bits += __shfl_xor(bits, o);
+  if (c.lane == 0)
+    W[c.wave * 16] = static_cast<unsigned long long>(bits);
+  long long nnz = 0, base_e = 0;  // base_e: the pointer of the chunk's first column
+  FpPrefix P = fp_prefix(n, 0);
+  unsigned long long acc = 0;
+  int c0 = 0, k = 0;
+  do
+  {
+    const int col = c0 + c.tid;
+    unsigned long long none = 0;
+    const int cnt = col < nx ? fp_x_column<false>(d, fos, sp, sr, mask, HP, HM, col, P, 0, none) : 0;
+    int inc = cnt;  // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+    {
+      const int v = __shfl_up(inc, o);
+      if (c.lane >= o)
+        inc += v;
+    }
+    const int slot = 2 + (k & 1);
+    if (c.lane == 63)
+      W[c.wave * 16 + slot] = static_cast<unsigned long long>(inc);
+    BSYNC();
+    if (k == 0)
+    {
+      long long b = 0;
+      for (int wv = 0; wv < kWaves; ++wv)
+        b += static_cast<long long>(W[wv * 16]);
+      nnz = fp_nnz(d, L.n_abs, b);
+      P = fp_prefix(n, nnz);
+    }
+    long long before = 0, total = 0;
+    for (int wv = 0; wv < kWaves; ++wv)
+    {
+      const long long t = static_cast<long long>(W[wv * 16 + slot]);
+      before += (wv < c.wave) ? t : 0;
+      total += t;
+    }
+    if (col < nx)
+    {
+      const long long e0 = base_e + before + (inc - cnt);
+      acc += fp_ptr_term(P, col, e0);
+      fp_x_column<true>(d, fos, sp, sr, mask, HP, HM, col, P, e0, acc);
+    }
+    base_e += total;
+    c0 += kBlock;
+    ++k;
+  } while (c0 < nx);
+  // columns >= nx and the end pointer, as far as a prefix reaches
+  const int last = fp_tail_last(d, P, base_e);
+  for (int col = nx + c.tid; col <= last; col += kBlock)
+    acc += fp_tail_column(d, P, base_e, col);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    acc += __shfl_xor(acc, o);
+  if (c.lane == 0)
+    W[c.wave * 16 + 1] = acc;
+  BSYNC();
+  if (c.tid == 0)
+  {
+    unsigned long long h = 0x6A09E667F3BCC908ULL;
+    for (int wv = 0; wv < kWaves; ++wv)
+      h += W[wv * 16 + 1];
+    fingerprint_compare(c, h, n, c.m(), nnz);
+  }
+}
+
 __device__ void sqp_optimize(Ctx& c, Solver& sv)
 {
   PROF(13);
@@ -6410,20 +6544,21 @@ __device__ void sqp_optimize(Ctx& c, Solver& sv)
         plan_lds_dynamic(c);
       build_and_scale(c);
       // pattern of A vs the previous QP setup, as OSQPModel tests it (quirk Q2)
-      BSYNC();
-      if (c.tid == 0)
       {
-        unsigned long long fh;
-        int fn, fm;
-        long long fz;
-        pattern_fingerprint(c, fh, fn, fm, fz);
-        c.s->flag = (fn == c.s->fp_n && fm == c.s->fp_m && fz == c.s->fp_nnz && fh == c.s->fp_hash) ? 1 : 0;
-        c.s->fp_n = fn;
-        c.s->fp_m = fm;
-        c.s->fp_nnz = fz;
-        c.s->fp_hash = fh;
+        PROF(40);
+        BSYNC();
+        if (!L.fp_ref)
+          pattern_fingerprint_wg(c);
+        else if (c.tid == 0)  // diagnostic (THIP_DEBUG_FP_REF): the serial walk
+        {
+          unsigned long long fh;
+          int fn, fm;
+          long long fz;
+          pattern_fingerprint(c, fh, fn, fm, fz);
+          fingerprint_compare(c, fh, fn, fm, fz);
+        }
+        BSYNC();
       }
-      BSYNC();
       bool pattern_equal = have_prev_setup && c.s->flag == 1;
       BSYNC();
       FOR(r, L.n_abs) pmask[r] = mask[r];
@@ -6474,6 +6609,8 @@ __device__ void sqp_optimize(Ctx& c, Solver& sv)
         }
         // model values at the QP solution (unscaled solution in A_SOLX)
         const double* SX = c.a(A_SOLX);
+        ProfSpan span(c);
+        span.begin();
         FOR(col, nx) XN[col] = SX[col];
         BSYNC();
         // JointVel model value (quadratic, exact), CartPose model values
@@ -6601,10 +6738,12 @@ __device__ void sqp_optimize(Ctx& c, Solver& sv)
           }
         }
         BSYNC();
+        span.end(41);
         evaluate(c, XN, NCOST, NVIOL);
         if (c.tid == 0)
           c.s->scan_at_x = 0;
         int decision = 0;  // 1 converged, 2 shrink, 3 accept
+        span.begin();
         if (c.tid == 0)
         {
           double oc = 0, mc = 0, nc = 0, ov = 0, mv = 0, nvv = 0;
@@ -6653,6 +6792,7 @@ __device__ void sqp_optimize(Ctx& c, Solver& sv)
           }
         }
         BSYNC();
+        span.end(42);
         decision = c.s->flag;
         BSYNC();
         if (decision == 1)

@@ -149,7 +149,7 @@ int thip_debug_set_path(int flags)
 {
   if (flags & ~(THIP_DEBUG_NO_SEGMENT | THIP_DEBUG_FORCE_WIDE | THIP_DEBUG_NO_BRANCH | THIP_DEBUG_STATIC_DISPATCH |
                 THIP_DEBUG_GEN_BUILD | THIP_DEBUG_MAIN_BUILD | THIP_DEBUG_SEG_REBUILD | THIP_DEBUG_SEG_RETURN |
-                THIP_DEBUG_SETUP_REF))
+                THIP_DEBUG_SETUP_REF | THIP_DEBUG_FP_REF))
     return THIP_E_INVALID;
   g_debug_path = flags;
   return THIP_OK;
@@ -846,6 +846,7 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     L.seg_rebuild = (g_debug_path & THIP_DEBUG_SEG_REBUILD) ? 1 : 0;
     L.seg_return = (g_debug_path & THIP_DEBUG_SEG_RETURN) ? 1 : 0;
     L.setup_ref = (g_debug_path & THIP_DEBUG_SETUP_REF) ? 1 : 0;
+    L.fp_ref = (g_debug_path & THIP_DEBUG_FP_REF) ? 1 : 0;
     L.tw_mid = L.sNb / 2;
     if (L.loff[A_LINV] < 0 || L.loff[A_CV] < 0 || L.loff[A_YV] < 0)
     {

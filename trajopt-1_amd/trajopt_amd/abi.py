@@ -38,6 +38,7 @@ DEBUG_MAIN_BUILD = 32
 DEBUG_SEG_REBUILD = 64  # the segment's packs rebuilt at every call (bitwise the same results)
 DEBUG_SEG_RETURN = 128  # the segment returns at every termination check, third infeasibility tests unused (same bits)
 DEBUG_SETUP_REF = 256  # the QP set-up's serial Ruiz column-norm loops, as before round 9 (same bits)
+DEBUG_FP_REF = 512  # the sparsity fingerprint from thread 0's serial walk, as before round 12 (same bits)
 
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_CONTINUOUS, JOINT_PRISMATIC = 0, 1, 2, 3
 PRIM_SPHERE, PRIM_BOX, PRIM_CAPSULE = 0, 1, 2

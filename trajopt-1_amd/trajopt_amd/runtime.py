@@ -169,7 +169,7 @@ class BatchTrustRegionSQP:
                      "gen_rhs_mr", "gen_rhs_cols", "gen_rhs_linv", "gen_dvalue_middle",
                      "n_primal_inf_full", "n_dual_inf_full", "n_factor", "gen_pre", "gen_updates",
                      "factor_blocks", "factor_twisted", "bwd_wave0_own", "gen_dvalue", "gen_middle_wait", "seg_setup", "seg_writeback",
-                     "n_seg_entries"]
+                     "n_seg_entries", "sqp_fingerprint", "sqp_model_values", "sqp_decide"]
 
     def layout(self):
         """The solve layout this context chose (thip_debug_solve_layout): branches, dofs
@@ -183,7 +183,7 @@ class BatchTrustRegionSQP:
         self._check(self.lib.thip_debug_profile(self.ctx, 1 if on else 0), "thip_debug_profile")
 
     def get_profile(self):
-        out = np.zeros((self.batch, 40), dtype=np.int64)
+        out = np.zeros((self.batch, len(self.PROFILE_SLOTS)), dtype=np.int64)  # csrc/layout.hpp kProfSlots
         self._check(self.lib.thip_debug_get_profile(self.ctx, out.ctypes.data_as(C.POINTER(C.c_longlong))),
                     "thip_debug_get_profile")
         return out
