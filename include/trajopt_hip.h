@@ -867,6 +867,7 @@ typedef struct thip_qp_info {
   double prim_res;
   double dual_res;
 } thip_qp_info;
+int thip_sizeof_qp_info(void); /* layout check of a binding's thip_qp_info mirror */
 /* Pattern (host arrays, copied): P_colptr[n+1], P_rowind[nnz_P] (rows <= column),
  * A_colptr[n+1], A_rowind[nnz_A]. */
 int thip_qp_create(int device, int n, int m, const int* P_colptr, const int* P_rowind, const int* A_colptr,

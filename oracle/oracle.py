@@ -235,6 +235,129 @@ def qp_solve(P, q, A, l, u, settings):
     return st, x, y[:m], it.value
 
 
+class QpInfoEx(C.Structure):
+    """orc::QpInfoEx (src/qp_session.hpp): thip_qp_info, rho_updates, polish_margin."""
+    _fields_ = [("info", abi.QpInfo), ("rho_updates", C.c_int), ("polish_margin", C.c_double)]
+
+
+def _qp_lib(variant):
+    L = lib(variant)
+    if not hasattr(L, "_qp_ready"):
+        ip = C.POINTER(C.c_int)
+        dp = C.POINTER(C.c_double)
+        sp = C.POINTER(abi.OsqpSettings)
+        xp = C.POINTER(QpInfoEx)
+        vp = C.c_void_p
+        L.oracle_sizeof_qp_info_ex.restype = C.c_int
+        assert L.oracle_sizeof_qp_info_ex() == C.sizeof(QpInfoEx), "QpInfoEx layout mismatch (rebuild the oracle)"
+        L.oracle_qp_solve_info.argtypes = [C.c_int, C.c_int, ip, ip, dp, dp, ip, ip, dp, dp, dp, sp, dp, dp,
+                                           C.c_double, dp, dp, xp]
+        L.oracle_qp_solve_info.restype = C.c_int
+        L.oracle_qp_session_new.argtypes = []
+        L.oracle_qp_session_new.restype = vp
+        L.oracle_qp_session_free.argtypes = [vp]
+        L.oracle_qp_session_free.restype = None
+        L.oracle_qp_session_setup.argtypes = [vp, C.c_int, C.c_int, ip, ip, dp, dp, ip, ip, dp, dp, dp, sp]
+        L.oracle_qp_session_setup.restype = C.c_int
+        L.oracle_qp_session_update_vec.argtypes = [vp, dp, dp, dp]
+        L.oracle_qp_session_update_vec.restype = C.c_int
+        L.oracle_qp_session_update_mat.argtypes = [vp, dp, dp]
+        L.oracle_qp_session_update_mat.restype = C.c_int
+        L.oracle_qp_session_warm_start.argtypes = [vp, dp, dp]
+        L.oracle_qp_session_warm_start.restype = C.c_int
+        L.oracle_qp_session_solve.argtypes = [vp, dp, dp, xp]
+        L.oracle_qp_session_solve.restype = C.c_int
+        L._qp_ready = True
+    return L
+
+
+def _f64(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _qp_arrays(P, q, A, l, u):
+    """(n, m, keep-alive list, the eleven pattern / value arguments) of a scipy CSC QP."""
+    ip = C.POINTER(C.c_int)
+    n, m = P.shape[0], A.shape[0]
+    ia = [np.ascontiguousarray(v, dtype=np.int32) for v in (P.indptr, P.indices, A.indptr, A.indices)]
+    va = [_f64(v) for v in (P.data, q, A.data, l, u)]
+    args = [n, m, ia[0].ctypes.data_as(ip), ia[1].ctypes.data_as(ip), _dp(va[0]), _dp(va[1]),
+            ia[2].ctypes.data_as(ip), ia[3].ctypes.data_as(ip), _dp(va[2]), _dp(va[3]), _dp(va[4])]
+    return n, m, ia + va, args
+
+
+def _qp_info_dict(ex):
+    i = ex.info
+    return {"status": i.status, "setup_error": i.setup_error, "polish_status": i.polish_status, "iter": i.iter,
+            "rho": i.rho, "prim_res": i.prim_res, "dual_res": i.dual_res, "rho_updates": ex.rho_updates,
+            "polish_margin": ex.polish_margin}
+
+
+def qp_solve_info(P, q, A, l, u, settings, warm_x=None, warm_y=None, warm_rho=None, variant="exact"):
+    """qp_solve with OSQPModel::createOrUpdateSolver's warm start (warm_rho into the
+    settings before the setup, then osqp_warm_start(warm_x, warm_y): both or
+    neither) -> (x, y, info): info holds every thip_qp_info field (status -1 and
+    setup_error when osqp_setup fails), rho_updates and polish_margin."""
+    L = _qp_lib(variant)
+    n, m, keep, args = _qp_arrays(P, q, A, l, u)
+    wx, wy = _f64(warm_x), _f64(warm_y)
+    x, y, ex = np.zeros(n), np.zeros(max(m, 1)), QpInfoEx()
+    rc = L.oracle_qp_solve_info(*args, C.byref(settings), _dp(wx), _dp(wy),
+                                float(warm_rho) if warm_rho is not None else 0.0, _dp(x), _dp(y), C.byref(ex))
+    if rc != 0:
+        raise RuntimeError("oracle_qp_solve_info: " + L.oracle_last_error().decode())
+    return x, y[:m], _qp_info_dict(ex)
+
+
+class QpSession:
+    """One OsqpSolver kept alive behind OSQP 1.0's update-in-place API, as
+    OsqpEigen::Solver keeps it: the reference of thip_qp_setup / update_vec /
+    update_mat / warm_start / solve_resident.  setup, update_vec, update_mat and
+    warm_start return the OSQP error code (0: fine; -1: there is no solver
+    object); solve returns (x, y, info) as qp_solve_info."""
+
+    def __init__(self, variant="exact"):
+        self._L = _qp_lib(variant)
+        self._h = self._L.oracle_qp_session_new()
+        self.n = self.m = 0
+
+    def close(self):
+        if self._h:
+            self._L.oracle_qp_session_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def setup(self, P, q, A, l, u, settings):
+        self.n, self.m, keep, args = _qp_arrays(P, q, A, l, u)
+        rc = self._L.oracle_qp_session_setup(self._h, *args, C.byref(settings))
+        if rc == -100:
+            raise RuntimeError("oracle_qp_session_setup: " + self._L.oracle_last_error().decode())
+        return rc
+
+    def update_vec(self, q=None, l=None, u=None):
+        q, l, u = _f64(q), _f64(l), _f64(u)
+        return self._L.oracle_qp_session_update_vec(self._h, _dp(q), _dp(l), _dp(u))
+
+    def update_mat(self, Px=None, Ax=None):
+        Px, Ax = _f64(Px), _f64(Ax)
+        rc = self._L.oracle_qp_session_update_mat(self._h, _dp(Px), _dp(Ax))
+        if rc == -100:
+            raise RuntimeError("oracle_qp_session_update_mat: " + self._L.oracle_last_error().decode())
+        return rc
+
+    def warm_start(self, x=None, y=None):
+        x, y = _f64(x), _f64(y)
+        return self._L.oracle_qp_session_warm_start(self._h, _dp(x), _dp(y))
+
+    def solve(self):
+        x, y, ex = np.zeros(self.n), np.zeros(max(self.m, 1)), QpInfoEx()
+        if self._L.oracle_qp_session_solve(self._h, _dp(x), _dp(y), C.byref(ex)) != 0:
+            raise RuntimeError("oracle_qp_session_solve: " + self._L.oracle_last_error().decode())
+        return x, y[:self.m], _qp_info_dict(ex)
+
+
 def swept_sphere_prim(a, b, r, prim):
     """(dist, normal, p_robot, t_star) of the sphere swept a -> b vs a primitive."""
     L = lib()

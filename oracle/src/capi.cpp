@@ -14,6 +14,7 @@
 #include "terms.hpp"
 #include "jitter.hpp"
 #include "osqp_restated.hpp"
+#include "qp_session.hpp"
 
 using namespace orc;
 
@@ -457,6 +458,78 @@ int oracle_qp_solve(int n, int m, const int* Pp, const int* Pi, const double* Px
     return -100;
   }
 }
+
+// oracle_qp_solve with OSQPModel's warm start (warm_x and warm_y both or neither,
+// warm_rho <= 0: settings->rho) and the whole thip_qp_info, rho_updates and
+// polish_margin (qp_session.hpp).  0, or -100 with oracle_last_error set.
+int oracle_qp_solve_info(int n, int m, const int* Pp, const int* Pi, const double* Px, const double* q, const int* Ap,
+                         const int* Ai, const double* Ax, const double* l, const double* u,
+                         const thip_osqp_settings* s, const double* warm_x, const double* warm_y, double warm_rho,
+                         double* x, double* y, QpInfoEx* out)
+{
+  try
+  {
+    qpSolveInfo(n, m, Pp, Pi, Px, q, Ap, Ai, Ax, l, u, *s, warm_x, warm_y, warm_rho, x, y, out);
+    return 0;
+  }
+  catch (const std::exception& ex)
+  {
+    g_err = ex.what();
+    return -100;
+  }
+}
+
+// oracle.QpSession: one OsqpSolver kept alive (qp_session.hpp)
+void* oracle_qp_session_new() { return new QpSession(); }
+void oracle_qp_session_free(void* h) { delete static_cast<QpSession*>(h); }
+int oracle_qp_session_setup(void* h, int n, int m, const int* Pp, const int* Pi, const double* Px, const double* q,
+                            const int* Ap, const int* Ai, const double* Ax, const double* l, const double* u,
+                            const thip_osqp_settings* s)
+{
+  try
+  {
+    return static_cast<QpSession*>(h)->setup(n, m, Pp, Pi, Px, q, Ap, Ai, Ax, l, u, *s);
+  }
+  catch (const std::exception& ex)
+  {
+    g_err = ex.what();
+    return -100;
+  }
+}
+int oracle_qp_session_update_vec(void* h, const double* q, const double* l, const double* u)
+{
+  return static_cast<QpSession*>(h)->update_vec(q, l, u);
+}
+int oracle_qp_session_update_mat(void* h, const double* Px, const double* Ax)
+{
+  try
+  {
+    return static_cast<QpSession*>(h)->update_mat(Px, Ax);
+  }
+  catch (const std::exception& ex)
+  {
+    g_err = ex.what();
+    return -100;
+  }
+}
+int oracle_qp_session_warm_start(void* h, const double* x, const double* y)
+{
+  return static_cast<QpSession*>(h)->warm_start(x, y);
+}
+int oracle_qp_session_solve(void* h, double* x, double* y, QpInfoEx* out)
+{
+  try
+  {
+    static_cast<QpSession*>(h)->solve(x, y, out);
+    return 0;
+  }
+  catch (const std::exception& ex)
+  {
+    g_err = ex.what();
+    return -100;
+  }
+}
+int oracle_sizeof_qp_info_ex() { return static_cast<int>(sizeof(QpInfoEx)); }
 
 int oracle_sizeof_desc() { return static_cast<int>(sizeof(thip_problem_desc)); }
 int oracle_sizeof_result() { return static_cast<int>(sizeof(thip_result)); }

@@ -13,10 +13,12 @@
 // Prints one line per check and exits with the number of failures.
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../src/kin.hpp"
+#include "../src/qp_session.hpp"
 #include "../src/sco.hpp"
 #include "../src/terms.hpp"
 
@@ -444,8 +446,61 @@ static void kat_kinematics()
   }
 }
 
+// A QpSession of setup + solve is the one-shot qpSolveInfo, bit for bit (both
+// are osqp_setup + osqp_solve on a fresh solver object), and stays so after an
+// update that puts the same data back.
+static void kat_qp_session()
+{
+  // minimise 2 x0^2 + x0 x1 + x1^2 + x0 + x1  s.t.  x0 + x1 = 1, 0 <= x0, x1 <= 0.7
+  const int n = 2, m = 3;
+  const int Pp[] = { 0, 1, 3 }, Pi[] = { 0, 0, 1 }, Ap[] = { 0, 2, 4 }, Ai[] = { 0, 1, 0, 2 };
+  const double Px[] = { 4, 1, 2 }, q[] = { 1, 1 }, Ax[] = { 1, 1, 1, 1 }, l[] = { 1, 0, 0 }, u[] = { 1, 0.7, 0.7 };
+  thip_osqp_settings s{};
+  s.rho = 0.1;
+  s.sigma = 1e-6;
+  s.alpha = 1.6;
+  s.scaling = 10;
+  s.adaptive_rho = 1;
+  s.adaptive_rho_tolerance = 5;
+  s.max_iter = 4000;
+  s.eps_abs = s.eps_rel = 1e-5;
+  s.eps_prim_inf = s.eps_dual_inf = 1e-4;
+  s.check_termination = 25;
+  s.warm_starting = 1;
+  s.polishing = 1;
+  s.delta = 1e-6;
+  s.polish_refine_iter = 3;
+  double x1[2], y1[3], x2[2], y2[3], x3[2], y3[3];
+  QpInfoEx i1, i2, i3;
+  qpSolveInfo(n, m, Pp, Pi, Px, q, Ap, Ai, Ax, l, u, s, nullptr, nullptr, 0, x1, y1, &i1);
+  QpSession ses;
+  CHECK(ses.setup(n, m, Pp, Pi, Px, q, Ap, Ai, Ax, l, u, s) == 0, "QpSession setup");
+  ses.solve(x2, y2, &i2);
+  auto same = [&](const double* x, const double* y, const QpInfoEx& i) {
+    return std::memcmp(x, x1, sizeof(x1)) == 0 && std::memcmp(y, y1, sizeof(y1)) == 0 &&
+           i.info.status == i1.info.status && i.info.iter == i1.info.iter &&
+           i.info.polish_status == i1.info.polish_status && i.info.rho == i1.info.rho &&
+           i.info.prim_res == i1.info.prim_res && i.info.dual_res == i1.info.dual_res &&
+           i.rho_updates == i1.rho_updates && i.polish_margin == i1.polish_margin;
+  };
+  CHECK(i1.info.status == OSQP_SOLVED && i1.info.polish_status == 1, "QpSession case is solved and polished");
+  NEAR(x1[0], 0.3, 1e-9, "QpSession case x0 = 0.3");
+  NEAR(x1[1], 0.7, 1e-9, "QpSession case x1 = 0.7");
+  CHECK(same(x2, y2, i2), "QpSession setup + solve == one-shot solve, bit for bit");
+  const double lbad[] = { 1, 0.8, 0 };
+  CHECK(ses.update_vec(nullptr, lbad, u) == 1 && ses.alive(), "QpSession l > u is rejected, the solver stays");
+  const double Pbad[] = { 4, 1, -1e6 };  // beyond what rho A^T A can make up for
+  CHECK(ses.update_mat(Pbad, nullptr) == 5 && !ses.alive(), "QpSession non-convex update loses the solver");
+  ses.solve(x3, y3, &i3);
+  CHECK(i3.info.status == -1 && i3.info.setup_error == 5, "QpSession solve without a solver reports -1 / 5");
+  CHECK(ses.setup(n, m, Pp, Pi, Px, q, Ap, Ai, Ax, l, u, s) == 0, "QpSession fresh setup");
+  ses.solve(x3, y3, &i3);
+  CHECK(same(x3, y3, i3), "QpSession fresh setup + solve == one-shot solve, bit for bit");
+}
+
 int main()
 {
+  kat_qp_session();
   kat_solver_utils();
   kat_modeling();
   kat_solver_interface();

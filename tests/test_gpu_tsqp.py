@@ -75,18 +75,7 @@ def test_synthetic_parity(gpu, oracle_mod, kind, seed):
 
 
 def _qp_lib():
-    L = abi.load_hip()
-    P = C.POINTER
-    dp, ip = P(C.c_double), P(C.c_int)
-    L.thip_qp_create.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, C.c_int, P(C.c_void_p)]
-    L.thip_qp_solve.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, P(abi.OsqpSettings), dp, dp, dp, dp, dp, C.c_void_p]
-    L.thip_qp_setup.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, P(abi.OsqpSettings), C.c_void_p]
-    L.thip_qp_update_vec.argtypes = [C.c_void_p, dp, dp, dp, C.c_void_p]
-    L.thip_qp_update_mat.argtypes = [C.c_void_p, dp, dp, C.c_void_p]
-    L.thip_qp_warm_start.argtypes = [C.c_void_p, dp, dp]
-    L.thip_qp_solve_resident.argtypes = [C.c_void_p, dp, dp, C.c_void_p]
-    L.thip_qp_destroy.argtypes = [C.c_void_p]
-    return L
+    return abi.load_hip()  # the thip_qp_* prototypes and the QpInfo mirror are abi.py's
 
 
 def test_resident_setup_equals_one_shot(gpu):
@@ -123,7 +112,7 @@ def test_resident_setup_equals_one_shot(gpu):
     ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))  # noqa: E731
     h = C.c_void_p()
     assert L.thip_qp_create(0, n, m, ip(Pp), ip(Pi), ip(Ap), ip(Ai), 1, C.byref(h)) == 0
-    info = (C.c_byte * 64)()
+    info = C.byref(abi.QpInfo())
     x1, y1 = np.zeros(n), np.zeros(m)
     assert L.thip_qp_solve(h, dp(Px), dp(q), dp(Ax), dp(lo), dp(up), C.byref(s), None, None, None, dp(x1), dp(y1),
                            info) == 0

@@ -2125,6 +2125,8 @@ int thip_qp_collect(thip_qp* q, double* x, double* y, thip_qp_info* info)
     info[b] = hinfo[static_cast<size_t>(b)];
     if (q->bad[static_cast<size_t>(b)])
     {
+      // osqp_setup refused the data: nothing of the launch's run on it is a result
+      info[b] = thip_qp_info{};
       info[b].status = -1;
       info[b].setup_error = 1;  // OSQP_DATA_VALIDATION_ERROR
     }
@@ -2420,5 +2422,7 @@ int thip_qp_shape(const thip_qp* q, long long* out)
   out[5] = static_cast<long long>(q->lds);
   return THIP_OK;
 }
+
+int thip_sizeof_qp_info(void) { return static_cast<int>(sizeof(thip_qp_info)); }
 
 }  // extern "C"

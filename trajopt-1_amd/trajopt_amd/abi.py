@@ -331,6 +331,20 @@ class TermSlot(C.Structure):
     ]
 
 
+class QpInfo(C.Structure):
+    """thip_qp_info (include/trajopt_hip.h): one generic QP's solve report."""
+
+    _fields_ = [
+        ("status", C.c_int),
+        ("setup_error", C.c_int),
+        ("polish_status", C.c_int),
+        ("iter", C.c_int),
+        ("rho", C.c_double),
+        ("prim_res", C.c_double),
+        ("dual_res", C.c_double),
+    ]
+
+
 def default_check_config() -> CheckConfig:
     """thip_default_check_config: one cast per step pair (CONTINUOUS), margin 0, every step."""
     return CheckConfig(CHECK_LVS_CONTINUOUS, float("inf"), 0.0, 0, -1)
@@ -537,6 +551,44 @@ def _declare(lib):
     lib.thip_debug_layout.restype = C.c_int
     lib.thip_debug_workspace.argtypes = [vp, dp, P(C.c_int)]
     lib.thip_debug_workspace.restype = C.c_int
+    # generic QP (thip_qp_*)
+    sp, qi, ll = P(OsqpSettings), P(QpInfo), P(C.c_longlong)
+    lib.thip_sizeof_qp_info.argtypes = []
+    lib.thip_sizeof_qp_info.restype = C.c_int
+    lib.thip_qp_create.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, C.c_int, P(vp)]
+    lib.thip_qp_create.restype = C.c_int
+    lib.thip_qp_solve.argtypes = [vp, dp, dp, dp, dp, dp, sp, dp, dp, dp, dp, dp, qi]
+    lib.thip_qp_solve.restype = C.c_int
+    lib.thip_qp_solve_some.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, sp, dp, dp, ip, dp, dp, dp, qi]
+    lib.thip_qp_solve_some.restype = C.c_int
+    lib.thip_qp_submit.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, sp, dp, dp, ip, dp]
+    lib.thip_qp_submit.restype = C.c_int
+    lib.thip_qp_collect.argtypes = [vp, dp, dp, qi]
+    lib.thip_qp_collect.restype = C.c_int
+    lib.thip_qp_stage.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, sp, dp, dp, ip, dp]
+    lib.thip_qp_stage.restype = C.c_int
+    lib.thip_qp_launch_staged.argtypes = [P(vp), C.c_int]
+    lib.thip_qp_launch_staged.restype = C.c_int
+    lib.thip_qp_destroy.argtypes = [vp]
+    lib.thip_qp_destroy.restype = None
+    lib.thip_qp_last_error.argtypes = [vp]
+    lib.thip_qp_last_error.restype = C.c_char_p
+    lib.thip_qp_factor_nnz.argtypes = [vp]
+    lib.thip_qp_factor_nnz.restype = C.c_longlong
+    lib.thip_qp_shape.argtypes = [vp, ll]
+    lib.thip_qp_shape.restype = C.c_int
+    lib.thip_qp_debug_profile.argtypes = [ll, C.c_int]
+    lib.thip_qp_debug_profile.restype = C.c_int
+    lib.thip_qp_setup.argtypes = [vp, dp, dp, dp, dp, dp, sp, qi]
+    lib.thip_qp_setup.restype = C.c_int
+    lib.thip_qp_update_vec.argtypes = [vp, dp, dp, dp, qi]
+    lib.thip_qp_update_vec.restype = C.c_int
+    lib.thip_qp_update_mat.argtypes = [vp, dp, dp, qi]
+    lib.thip_qp_update_mat.restype = C.c_int
+    lib.thip_qp_warm_start.argtypes = [vp, dp, dp]
+    lib.thip_qp_warm_start.restype = C.c_int
+    lib.thip_qp_solve_resident.argtypes = [vp, dp, dp, qi]
+    lib.thip_qp_solve_resident.restype = C.c_int
     lib.thip_sizeof_desc.argtypes = []
     lib.thip_sizeof_desc.restype = C.c_int
     lib.thip_sizeof_result.argtypes = []
@@ -571,6 +623,8 @@ def load_hip():
             raise RuntimeError("thip_term_slot layout mismatch between Python and the HIP library")
         if _hip.thip_sizeof_csets_config() != C.sizeof(CsetsConfig):
             raise RuntimeError("thip_csets_config layout mismatch between Python and the HIP library")
+        if _hip.thip_sizeof_qp_info() != C.sizeof(QpInfo):
+            raise RuntimeError("thip_qp_info layout mismatch between Python and the HIP library")
     return _hip
 
 
