@@ -1023,6 +1023,89 @@ double thip_csets_last_ms(thip_csets* cs);
 void thip_csets_destroy(thip_csets* cs);
 const char* thip_csets_last_error(thip_csets* cs); /* NULL: the last thip_csets_create failure */
 
+/* -------------------------------------------- Continuous collision sets
+ * The rows of trajopt_ifopt's fixed-size ContinuousCollisionConstraint over an
+ * LVSContinuousCollisionEvaluator or LVSDiscreteCollisionEvaluator
+ * (trajopt_ifopt/src/constraints/collision/continuous_collision_evaluators.cpp:
+ * 97-248, 317-458, continuous_collision_constraint.cpp:80-236, trajopt_common/
+ * src/collision_utils.cpp:73-221, collision_types.cpp:128-330,
+ * weighted_average_methods.cpp:31-107) for every segment (t, t + 1), t in
+ * [first_step, last_step - 1], of every problem of a batch, in one launch, on
+ * the primitive collision model.  The descriptor fields read, the coll_pairs
+ * (term 0) overrides and the key convention are those of thip_csets.
+ *
+ * Sub-states and contacts of a segment are those of the collision terms
+ * (thip_eval_collision) for the same evaluator type, contact test ALL:
+ * cnt = 2 states, or ceil(|q1 - q0| / lvs) + 1 when |q1 - q0| > lvs (CONTINUOUS:
+ * always 2); LVS_DISCRETE tests each of the cnt states, the continuous types
+ * the cnt - 1 casts between consecutive states.  A contact is kept when its
+ * pair's coefficient is not zero and distance < margin(pair) + margin_buffer,
+ * and, at a segment with a fixed end, when one of its robot sides is not at
+ * that end (removeInvalidContactResults).
+ *
+ * One set per key (link, other, sphere, other_sphere) holds that key's kept
+ * contacts in sub-state order, error = margin(pair) - distance.  Per side whose
+ * link a joint moves and per end e the set keeps the maximum error over its
+ * contacts whose cc_type on that side is not Time1 (e = 0) / not Time0 (e = 1).
+ * The set's value E is the maximum over all sides and ends (both ends free) or
+ * over the sides at the free end.  Rows: E descending, ties by key ascending
+ * (this build's fixed choice, as for thip_csets), the first R = max_num_cnt
+ * sets.  A set without an error at the free end ranks last, value
+ * -margin_buffer, zero rows.
+ *
+ * The row of a set at end e is zero when that end is fixed, else
+ * -(sum w scale g) / (sum w) over its (contact, side) pairs whose side has a
+ * gradient, whose cc_type is not Time1 (e = 0) / not Time0 (e = 1) and whose
+ * side's maximum error + margin_buffer at e is positive; w = max(error +
+ * margin_buffer, 0) / (E + margin_buffer), scale = 1 - cc_time (e = 0) or
+ * cc_time (e = 1), g = the side's distance gradient with the link's jacobian at
+ * q0 (Time0), q1 (Time1) or q0 + (q1 - q0) cc_time, moved to the contact point
+ * of the sub-state's start pose (e = 0) or end pose (e = 1).  The row is zero
+ * when no pair qualifies, when E + margin_buffer <= 0 or when sum w = 0.
+ *
+ * A segment that needs more than THIP_CCSETS_MAX_SUBSTATES states gets
+ * counts = -1 and padded rows, and the run returns THIP_E_INVALID naming the
+ * first such problem and segment.
+ *
+ * Outputs, n = last_step - first_step segments (any may be NULL):
+ *   values [batch][n][R]            E; -margin_buffer in rows >= counts
+ *   jac    [batch][n][R][2][n_dof]  end 0 = node t, end 1 = node t + 1
+ *   coeffs [batch][n][R]            coeff(pair); 1 in rows >= counts
+ *   counts [batch][n]               sets before truncation
+ *   keys   [batch][n][R][4]         -1 in rows >= counts
+ * Bitwise repeatable; a problem's rows do not depend on its position in the
+ * batch or on `batch`. */
+#define THIP_CCSETS_MAX_SUBSTATES 4096
+/* evaluator_type: tesseract's CollisionEvaluatorType values, as the front door's evaluator_type */
+#define THIP_EVALUATOR_LVS_DISCRETE 2
+#define THIP_EVALUATOR_CONTINUOUS 3
+#define THIP_EVALUATOR_LVS_CONTINUOUS 4
+typedef struct thip_ccsets_config {
+  double margin, coeff, margin_buffer;
+  int max_num_cnt;                     /* rows per segment, 1 .. THIP_CSETS_MAX_ROWS */
+  int first_step, last_step;           /* segments (t, t + 1), first_step <= t < last_step, both in [0, n_steps) */
+  int evaluator_type;                  /* THIP_EVALUATOR_* */
+  double longest_valid_segment_length; /* finite, > 0 (not read by CONTINUOUS) */
+} thip_ccsets_config;
+
+typedef struct thip_ccsets thip_ccsets;
+void thip_default_ccsets_config(thip_ccsets_config* c); /* csets' defaults, nodes 0..1, LVS_CONTINUOUS, lvs 0.005 */
+int thip_sizeof_ccsets_config(void);
+/* seg_fixed [last_step - first_step]: bit 0 = vars0 fixed, bit 1 = vars1 fixed; NULL: none.
+ * Validates cfg, seg_fixed and every descriptor field read before any device call. */
+int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccsets_config* cfg, const int* seg_fixed,
+                       int batch, thip_ccsets** out);
+int thip_ccsets_upload(thip_ccsets* cs, const double* scene);
+int thip_ccsets_upload_device(thip_ccsets* cs, const double* d_scene);
+int thip_ccsets_segments(const thip_ccsets* cs); /* last_step - first_step */
+int thip_ccsets_run(thip_ccsets* cs, const double* x, double* values, double* jac, double* coeffs, int* counts,
+                    int* keys);
+int thip_ccsets_run_device(thip_ccsets* cs, const double* d_x, double* values, double* jac, double* coeffs,
+                           int* counts, int* keys);
+double thip_ccsets_last_ms(thip_ccsets* cs);
+void thip_ccsets_destroy(thip_ccsets* cs);
+const char* thip_ccsets_last_error(thip_ccsets* cs); /* NULL: the last thip_ccsets_create failure */
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,19 @@ typedef struct tsqp_coll_term {
   int max_num_cnt, fixed_sparsity;
   double margin, coeff, buffer;       /* TrajOptCollisionConfig(margin, coeff), collision_margin_buffer */
 } tsqp_coll_term;
+typedef struct tsqp_ccoll_term {
+  int first, last;                    /* one ContinuousCollisionConstraint per segment (n, n + 1), first <= n < last,
+                                         all on one evaluator */
+  int penalty;
+  int max_num_cnt, fixed_sparsity;
+  int evaluator_type;                 /* tesseract's CollisionEvaluatorType: DISCRETE 1 / LVS_DISCRETE 2 go to an
+                                         LVSDiscreteCollisionEvaluator, every other value to an
+                                         LVSContinuousCollisionEvaluator (CONTINUOUS 3, LVS_CONTINUOUS 4); each
+                                         refuses the types it does not take */
+  int fixed_first, fixed_last;        /* vars0_fixed of the first segment, vars1_fixed of the last */
+  double margin, coeff, buffer;       /* TrajOptCollisionConfig(margin, coeff), collision_margin_buffer */
+  double lvs_length;                  /* collision_check_config.longest_valid_segment_length */
+} tsqp_ccoll_term;
 typedef struct tsqp_kin_spec {
   char manip[TSQP_KIN_NAME_LEN];
   int n_prims;
@@ -259,15 +272,18 @@ typedef struct tsqp_kin_spec {
   tsqp_cart_term cart[TSQP_KIN_MAX_CART];
   int n_coll;
   tsqp_coll_term coll[TSQP_KIN_MAX_COLL];
+  int n_ccoll;
+  tsqp_ccoll_term ccoll[TSQP_KIN_MAX_COLL];
 } tsqp_kin_spec;
 /* thost_tsqp_solve with the kinematic sets added after the joint terms (the
- * CartPos sets, then each collision term's nodes) */
+ * CartPos sets, then each collision term's nodes, then each continuous collision
+ * term's segments) */
 int thost_tsqp_solve_kin(const tsqp_spec* spec, const tsqp_kin_spec* kin, int device, double* x, tsqp_result* result,
                          char* err, int err_len);
 /* The same sets without a solve: for each of the n_x variable vectors xs
  * [n_x][n_nodes][n_dof], set in turn with TrajOptQPProblem::setVariables, every
  * set's getValues, dense getJacobian and getCoefficients, rows concatenated in
- * set order (joint terms, CartPos sets, collision nodes):
+ * set order (joint terms, CartPos sets, collision nodes, continuous collision segments):
  *   n_sets, set_rows [cap_sets]          the sets and their row counts
  *   values, coeffs [n_x][cap_rows]       jac [n_x][cap_rows][n_nodes * n_dof]
  *   lower, upper [cap_rows]              getBounds (+-inf as +-HUGE_VAL)
@@ -286,6 +302,7 @@ int thost_tsqp_eval_kin(const tsqp_spec* spec, const tsqp_kin_spec* kin, int dev
 int thost_tsqp_sizeof_kin_spec(void);
 int thost_tsqp_sizeof_cart_term(void);
 int thost_tsqp_sizeof_coll_term(void);
+int thost_tsqp_sizeof_ccoll_term(void);
 
 #ifdef __cplusplus
 }

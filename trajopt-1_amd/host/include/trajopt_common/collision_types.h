@@ -38,6 +38,8 @@ struct TrajOptCollisionConfig
   double collision_margin{ 0.0 };  // contact_manager_config's default margin
   double collision_coeff{ 1.0 };   // collision_coeff_data's default coefficient
   CollisionEvaluatorType type{ CollisionEvaluatorType::DISCRETE };  // collision_check_config.type
+  // collision_check_config.longest_valid_segment_length (the LVS evaluators' sub-states)
+  double longest_valid_segment_length{ 0.005 };
   // added to every margin for the contact test, not used in the error
   double collision_margin_buffer{ 0.01 };
   // CollisionMarginData::setCollisionMargin + CollisionCoeffData::setCollisionCoeff of

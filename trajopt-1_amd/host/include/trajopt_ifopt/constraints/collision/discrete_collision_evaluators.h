@@ -7,7 +7,8 @@
 // first update() or getValues() at new variable values launches once over all
 // those nodes; each constraint reads its node's rows.
 // tesseract's JointGroup / Environment are trajopt::KinematicGroup /
-// trajopt::Environment.  The LVS and continuous evaluators are not built.
+// trajopt::Environment.  The LVS and continuous evaluators are in
+// continuous_collision_evaluators.h.
 #pragma once
 #include <memory>
 #include <vector>
@@ -18,6 +19,13 @@
 
 namespace trajopt_ifopt
 {
+// The descriptor fields thip_csets_create / thip_ccsets_create read, lowered from the
+// group, the environment and the config's pair entries (no device call): the
+// lowering of every collision evaluator.
+void lowerCollisionSets(const trajopt::KinematicGroup& manip, const trajopt::Environment& env,
+                        const trajopt_common::TrajOptCollisionConfig& config, int n_steps, thip_problem_desc& desc,
+                        std::vector<double>& scene);
+
 class DiscreteCollisionEvaluator
 {
 public:

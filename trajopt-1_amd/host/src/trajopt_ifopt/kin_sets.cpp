@@ -468,9 +468,19 @@ SingleTimestepCollisionEvaluator::~SingleTimestepCollisionEvaluator()
 
 void SingleTimestepCollisionEvaluator::lower(thip_problem_desc& d, std::vector<double>& scene) const
 {
+  lowerCollisionSets(*manip_, *env_, config_, std::max<int>(1, static_cast<int>(vars_.size())), d, scene);
+}
+
+void lowerCollisionSets(const trajopt::KinematicGroup& manip, const trajopt::Environment& env,
+                        const trajopt_common::TrajOptCollisionConfig& config, int n_steps, thip_problem_desc& d,
+                        std::vector<double>& scene)
+{
+  const trajopt::KinematicGroup* manip_ = &manip;
+  const trajopt::Environment* env_ = &env;
+  const trajopt_common::TrajOptCollisionConfig& config_ = config;
   std::memset(&d, 0, sizeof(d));
   d.abi_version = THIP_ABI_VERSION;
-  d.n_steps = std::max<int>(1, static_cast<int>(vars_.size()));
+  d.n_steps = n_steps;
   d.chain = manip_->chain;
   scene.clear();
   trajopt::lowerCollisionModel(*manip_, *env_, d, scene);

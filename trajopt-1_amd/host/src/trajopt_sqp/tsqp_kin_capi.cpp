@@ -1,7 +1,7 @@
 // C entry points of the trajopt_sqp front end's kinematic sets
 // (include/trajopt_host.h, tsqp_kin_*): a tsqp_spec's joint terms plus
-// CartPosConstraint sets and fixed-size DiscreteCollisionConstraint sets on the
-// built-in environment of a group -- the setups of the reference's
+// CartPosConstraint sets and fixed-size DiscreteCollisionConstraint and
+// ContinuousCollisionConstraint sets on the built-in environment of a group -- the setups of the reference's
 // cart_position_optimization_unit, numerical_ik_unit and simple_collision_unit
 // (trajopt_optimizers/trajopt_sqp/test/).
 #include <cmath>
@@ -14,6 +14,7 @@
 
 #include "trajopt_host.h"
 #include "trajopt_ifopt/constraints/cartesian_position_constraint.h"
+#include "trajopt_ifopt/constraints/collision/continuous_collision_constraint.h"
 #include "trajopt_ifopt/constraints/collision/discrete_collision_constraint.h"
 #include "tsqp_build.h"
 
@@ -39,6 +40,7 @@ struct KinBuilt
   std::shared_ptr<DeviceSetEvaluator> cart_eval;
   std::vector<std::shared_ptr<CartPosConstraint>> cart;
   std::vector<std::shared_ptr<DiscreteCollisionEvaluator>> coll_evals;
+  std::vector<std::shared_ptr<ContinuousCollisionEvaluator>> ccoll_evals;
 };
 
 void addSet(trajopt_sqp::capi::Built& b, const std::shared_ptr<ConstraintSet>& cs, int penalty, const std::string& w)
@@ -67,7 +69,7 @@ KinBuilt buildKin(const tsqp_spec* s, const tsqp_kin_spec* k, int device, const 
 {
   const std::string w(who);
   if (k->n_prims < 0 || k->n_prims > TSQP_KIN_MAX_PRIMS || k->n_cart < 0 || k->n_cart > TSQP_KIN_MAX_CART ||
-      k->n_coll < 0 || k->n_coll > TSQP_KIN_MAX_COLL)
+      k->n_coll < 0 || k->n_coll > TSQP_KIN_MAX_COLL || k->n_ccoll < 0 || k->n_ccoll > TSQP_KIN_MAX_COLL)
     throw std::runtime_error(w + ": kinematic spec out of range");
   KinBuilt out;
   out.joint = trajopt_sqp::capi::buildJointProblem(s, who);
@@ -127,6 +129,33 @@ KinBuilt buildKin(const tsqp_spec* s, const tsqp_kin_spec* k, int device, const 
                                                            t.max_num_cnt, t.fixed_sparsity != 0,
                                                            "DiscreteCollision_" + std::to_string(i) + "_" +
                                                                std::to_string(n)),
+             t.penalty, w);
+  }
+  for (int i = 0; i < k->n_ccoll; ++i)
+  {
+    const tsqp_ccoll_term& t = k->ccoll[i];
+    if (t.first < 0 || t.last <= t.first || t.last >= s->n_nodes)
+      throw std::runtime_error(w + ": continuous collision term " + std::to_string(i) + ": nodes out of range");
+    using trajopt_common::CollisionEvaluatorType;
+    trajopt_common::TrajOptCollisionConfig cfg(t.margin, t.coeff);
+    cfg.collision_margin_buffer = t.buffer;
+    cfg.longest_valid_segment_length = t.lvs_length;
+    cfg.type = (t.evaluator_type >= 0 && t.evaluator_type <= 4) ? static_cast<CollisionEvaluatorType>(t.evaluator_type)
+                                                                : CollisionEvaluatorType::NONE;
+    std::shared_ptr<ContinuousCollisionEvaluator> ev;
+    if (cfg.type == CollisionEvaluatorType::DISCRETE || cfg.type == CollisionEvaluatorType::LVS_DISCRETE)
+      ev = std::make_shared<LVSDiscreteCollisionEvaluator>(kin, out.env, cfg);
+    else
+      ev = std::make_shared<LVSContinuousCollisionEvaluator>(kin, out.env, cfg);
+    out.ccoll_evals.push_back(ev);
+    for (int n = t.first; n < t.last; ++n)
+      addSet(out.joint,
+             std::make_shared<ContinuousCollisionConstraint>(
+                 ev,
+                 std::array<std::shared_ptr<const Var>, 2>{ out.joint.vars[static_cast<std::size_t>(n)],
+                                                            out.joint.vars[static_cast<std::size_t>(n) + 1] },
+                 n == t.first && t.fixed_first != 0, n + 1 == t.last && t.fixed_last != 0, t.max_num_cnt,
+                 t.fixed_sparsity != 0, "LVSCollision_" + std::to_string(i) + "_" + std::to_string(n)),
              t.penalty, w);
   }
   return out;
@@ -235,6 +264,8 @@ int thost_tsqp_eval_kin(const tsqp_spec* s, const tsqp_kin_spec* k, int device, 
       launches[1] = 0;
       for (const auto& ev : b.coll_evals)
         launches[1] += ev->launches();
+      for (const auto& ev : b.ccoll_evals)
+        launches[1] += ev->launches();
     }
     return 0;
   }
@@ -248,4 +279,5 @@ int thost_tsqp_eval_kin(const tsqp_spec* s, const tsqp_kin_spec* k, int device, 
 int thost_tsqp_sizeof_kin_spec(void) { return static_cast<int>(sizeof(tsqp_kin_spec)); }
 int thost_tsqp_sizeof_cart_term(void) { return static_cast<int>(sizeof(tsqp_cart_term)); }
 int thost_tsqp_sizeof_coll_term(void) { return static_cast<int>(sizeof(tsqp_coll_term)); }
+int thost_tsqp_sizeof_ccoll_term(void) { return static_cast<int>(sizeof(tsqp_ccoll_term)); }
 }  // extern "C"

@@ -5,7 +5,10 @@
 // CartPosConstraint, SingleTimestepCollisionEvaluator and
 // DiscreteCollisionConstraint, the RangeBoundHandling split, and
 // thip_csets_create's validation with out-of-range steps and max_num_cnt, a
-// non-finite margin and an inverted range, at the ends of int's range.  Every
+// non-finite margin and an inverted range, at the ends of int's range; the same
+// for the continuous sets (LVSContinuousCollisionEvaluator,
+// LVSDiscreteCollisionEvaluator, ContinuousCollisionConstraint,
+// thip_ccsets_create with coll_sets_cont.hip's host code compiled in).  Every
 // refusal must carry its message and come before any device call, so no GPU is
 // needed; the sanitizers turn memory errors and signed overflow into a non-zero
 // exit.
@@ -20,6 +23,7 @@
 #include <string>
 
 #include "trajopt_ifopt/constraints/cartesian_position_constraint.h"
+#include "trajopt_ifopt/constraints/collision/continuous_collision_constraint.h"
 #include "trajopt_ifopt/constraints/collision/discrete_collision_constraint.h"
 
 namespace
@@ -253,6 +257,141 @@ int main()
     thip_csets* cs = nullptr;
     expect(thip_csets_create(0, d.get(), &good, INT_MIN, &cs) == THIP_E_INVALID, "batch");
     expect(thip_csets_create(0, nullptr, &good, 1, &cs) == THIP_E_INVALID, "null descriptor");
+  }
+
+  // ---- the continuous evaluators, their fixed-size set and thip_ccsets_create
+  {
+    using trajopt_common::CollisionEvaluatorType;
+    using Two = std::array<std::shared_ptr<const Var>, 2>;
+    Vars v = makeVars(3, 7);
+    trajopt_common::TrajOptCollisionConfig disc(0.1, 1.0);
+    trajopt_common::TrajOptCollisionConfig lvsd(0.1, 1.0, CollisionEvaluatorType::LVS_DISCRETE);
+    trajopt_common::TrajOptCollisionConfig lvsc(0.1, 1.0, CollisionEvaluatorType::LVS_CONTINUOUS);
+    trajopt_common::TrajOptCollisionConfig cont(0.1, 1.0, CollisionEvaluatorType::CONTINUOUS);
+    refused([&] { LVSContinuousCollisionEvaluator(kin, env, disc); },
+            "LVSContinuousCollisionEvaluator, should be configured with CONTINUOUS or LVS_CONTINUOUS");
+    refused([&] { LVSContinuousCollisionEvaluator(kin, env, lvsd); },
+            "LVSContinuousCollisionEvaluator, should be configured with CONTINUOUS or LVS_CONTINUOUS");
+    refused([&] { LVSDiscreteCollisionEvaluator(kin, env, lvsc); },
+            "LVSDiscreteCollisionEvaluator, should be configured with LVS_DISCRETE");
+    refused([&] { LVSDiscreteCollisionEvaluator(kin, env, cont); },
+            "LVSDiscreteCollisionEvaluator, should be configured with LVS_DISCRETE");
+    refused([&] { LVSContinuousCollisionEvaluator(nullptr, env, lvsc); }, "null kinematic group");
+    auto bare = std::make_shared<trajopt::Environment>();
+    bare->addJointGroup(*kin);
+    refused([&] { LVSContinuousCollisionEvaluator(bare->getJointGroup("right_arm"), bare, lvsc); },
+            "sphere model is missing");
+    LVSContinuousCollisionEvaluator one_cast(kin, env, cont);
+    LVSDiscreteCollisionEvaluator lvs_discrete(kin, env, lvsd);
+    auto ev = std::make_shared<LVSContinuousCollisionEvaluator>(kin, env, lvsc);
+    expect(ev->getCollisionMarginBuffer() == 0.01 && ev->launches() == 0, "default buffer, no launch");
+    const Two seg01{ v.vars[0], v.vars[1] }, seg12{ v.vars[1], v.vars[2] };
+    refused([&] { ContinuousCollisionConstraint(ev, Two{ nullptr, v.vars[1] }, false, false); },
+            "position_vars contains a nullptr!");
+    refused([&] { ContinuousCollisionConstraint(ev, Two{ v.vars[0], nullptr }, false, false); },
+            "position_vars contains a nullptr!");
+    refused([&] { ContinuousCollisionConstraint(nullptr, seg01, false, false); }, "null evaluator");
+    refused([&] { ContinuousCollisionConstraint(ev, seg01, true, true); }, "both ends cannot be fixed!");
+    refused([&] { ContinuousCollisionConstraint(ev, seg01, false, false, 0); }, "max_num_cnt must be greater than zero!");
+    refused([&] { ContinuousCollisionConstraint(ev, seg01, false, false, INT_MIN); },
+            "max_num_cnt must be greater than zero!");
+    refused([&] { ContinuousCollisionConstraint(ev, seg01, false, false, INT_MAX); }, "rows per segment");
+    refused([&] { ContinuousCollisionConstraint(ev, Two{ v.vars[0], v.vars[2] }, false, false); },
+            "not consecutive nodes");
+    refused([&] { ContinuousCollisionConstraint(ev, Two{ v.vars[1], v.vars[0] }, false, false); },
+            "not consecutive nodes");
+    {
+      Vars w = makeVars(2, 2);
+      refused([&] { ContinuousCollisionConstraint(ev, Two{ w.vars[0], w.vars[1] }, false, false); }, "the group 7 joints");
+      Vars u = makeVars(2, 7);
+      refused([&] { ContinuousCollisionConstraint(ev, Two{ v.vars[0], u.vars[1] }, false, false); },
+              "all vars must belong to the same variable set");
+      Vars m = makeVars(1, 5);
+      refused([&] { ContinuousCollisionConstraint(ev, Two{ v.vars[0], m.vars[0] }, false, false); },
+              "all position_vars must have same size!");
+    }
+    ContinuousCollisionConstraint c(ev, seg01, true, false, 3, true);
+    expect(c.getRows() == 3 && c.getCoefficients() == VectorXd(3, 1.0) && c.getNonZeros() == 2 * 3 * 7,
+           "three rows of ones over two nodes");
+    expect(c.getBounds()[2].getType() == BoundsType::kUpperBound && c.getBounds()[2].getUpper() == 0.0, "BoundSmallerZero");
+    refused([&] { c.setBounds(std::vector<Bounds>(2, BoundZero)); }, "2 bounds for 3 rows");
+    refused([&] { ContinuousCollisionConstraint(ev, seg01, false, true, 3); }, "registered twice with different fixed ends");
+    {
+      Vars w = makeVars(2, 7);  // another variable set on the same evaluator
+      refused([&] { ContinuousCollisionConstraint(ev, Two{ w.vars[0], w.vars[1] }, false, false); },
+              "must share one NodesVariables");
+    }
+    refused([&] { ev->rows(*v.vars[1], *v.vars[2]); }, "was not registered");
+    ContinuousCollisionConstraint c2(ev, seg12, false, true, 2);
+
+    // ---- thip_ccsets_create: every refusal before any device call
+    auto d = std::make_unique<thip_problem_desc>();
+    std::vector<double> scene;
+    ev->lower(*d, scene);
+    expect(d->n_spheres == 14 && d->n_steps == 3, "lowered");
+    thip_ccsets_config good{ 0.1, 1.0, 0.01, 3, 0, 2, THIP_EVALUATOR_LVS_CONTINUOUS, 0.05 };
+    auto refusedC = [&](const thip_problem_desc& desc, const thip_ccsets_config& cfg, const int* fixed,
+                        const char* needle) {
+      thip_ccsets* cs = nullptr;
+      const int rc = thip_ccsets_create(0, &desc, &cfg, fixed, 1, &cs);
+      const char* msg = thip_ccsets_last_error(nullptr);
+      expect(rc == THIP_E_INVALID && cs == nullptr && std::strstr(msg, needle) != nullptr,
+             std::string("thip_ccsets_create: rc ") + std::to_string(rc) + " '" + msg + "' lacks '" + needle + "'");
+      if (cs)
+        thip_ccsets_destroy(cs);
+    };
+    auto with = [&](std::function<void(thip_ccsets_config&)> f) {
+      thip_ccsets_config k = good;
+      f(k);
+      return k;
+    };
+    for (int et : { INT_MIN, -1, 0, 1, 5, INT_MAX })
+      refusedC(*d, with([=](auto& k) { k.evaluator_type = et; }), nullptr, "evaluator_type");
+    for (double l : { 0.0, -1.0, static_cast<double>(NAN), inf, -inf })
+      refusedC(*d, with([=](auto& k) { k.longest_valid_segment_length = l; }), nullptr, "must be finite and > 0");
+    for (int n : { 0, THIP_CSETS_MAX_ROWS + 1, INT_MIN, INT_MAX })
+      refusedC(*d, with([=](auto& k) { k.max_num_cnt = n; }), nullptr, "out of range [1, 64]");
+    refusedC(*d, with([](auto& k) { k.first_step = 1, k.last_step = 1; }), nullptr, "holds no segment");
+    refusedC(*d, with([](auto& k) { k.first_step = 2, k.last_step = 0; }), nullptr, "holds no segment");
+    refusedC(*d, with([](auto& k) { k.first_step = -1; }), nullptr, "outside [0, 2]");
+    refusedC(*d, with([](auto& k) { k.last_step = 3; }), nullptr, "outside [0, 2]");
+    refusedC(*d, with([](auto& k) { k.first_step = INT_MIN, k.last_step = INT_MAX; }), nullptr, "outside [0, 2]");
+    refusedC(*d, with([](auto& k) { k.first_step = INT_MAX, k.last_step = INT_MIN; }), nullptr, "outside [0, 2]");
+    refusedC(*d, with([](auto& k) { k.last_step = INT_MAX; }), nullptr, "outside [0, 2]");
+    refusedC(*d, with([](auto& k) { k.margin = std::nan(""); }), nullptr, "margin is not finite");
+    refusedC(*d, with([=](auto& k) { k.coeff = -inf; }), nullptr, "coeff is not finite");
+    refusedC(*d, with([=](auto& k) { k.margin_buffer = inf; }), nullptr, "margin_buffer is not finite");
+    {
+      const int f3[2] = { 0, 3 }, fneg[2] = { INT_MIN, 0 }, fbig[2] = { 0, INT_MAX };
+      refusedC(*d, good, f3, "seg_fixed[1]: both ends cannot be fixed!");
+      refusedC(*d, good, fneg, "seg_fixed[0]");
+      refusedC(*d, good, fbig, "seg_fixed[1]");
+    }
+    {
+      auto e = std::make_unique<thip_problem_desc>(*d);
+      e->n_spheres = 0;
+      refusedC(*e, good, nullptr, "no robot spheres");
+      *e = *d;
+      e->abi_version = THIP_ABI_VERSION - 1;
+      refusedC(*e, good, nullptr, "abi_version");
+      *e = *d;
+      e->n_steps = INT_MAX;
+      refusedC(*e, good, nullptr, "n_steps out of range");
+      *e = *d;
+      e->n_prims = INT_MIN;
+      refusedC(*e, good, nullptr, "n_prims out of range");
+      *e = *d;
+      e->sphere_link[0] = INT_MAX;
+      refusedC(*e, good, nullptr, "bad sphere link");
+      *e = *d;
+      e->self_pair[1][0] = e->self_pair[0][1];
+      e->self_pair[1][1] = e->self_pair[0][0];
+      refusedC(*e, good, nullptr, "self_pair[1] repeats self_pair[0]");
+    }
+    thip_ccsets* cs = nullptr;
+    expect(thip_ccsets_create(0, d.get(), &good, nullptr, INT_MIN, &cs) == THIP_E_INVALID, "batch");
+    expect(thip_ccsets_create(0, nullptr, &good, nullptr, 1, &cs) == THIP_E_INVALID, "null descriptor");
+    expect(thip_ccsets_segments(nullptr) == THIP_E_INVALID && thip_ccsets_last_ms(nullptr) < 0, "null object");
   }
   std::printf("ifopt_sets_san: %d failures\n", g_failures);
   return g_failures ? 1 : 0;

@@ -315,6 +315,27 @@ class CsetsConfig(C.Structure):
     ]
 
 
+CCSETS_MAX_SUBSTATES = 4096  # THIP_CCSETS_MAX_SUBSTATES: states of one segment of a continuous collision set
+# thip_ccsets_config.evaluator_type (THIP_EVALUATOR_*: tesseract's CollisionEvaluatorType values)
+EVALUATOR_LVS_DISCRETE, EVALUATOR_CONTINUOUS, EVALUATOR_LVS_CONTINUOUS = 2, 3, 4
+
+
+class CcsetsConfig(C.Structure):
+    """thip_ccsets_config: the continuous collision sets of thip_ccsets_* (margin / coeff /
+    buffer, rows per segment, the segments (t, t + 1) of first_step <= t < last_step, the
+    evaluator type and its longest valid segment length)."""
+    _fields_ = [
+        ("margin", C.c_double),
+        ("coeff", C.c_double),
+        ("margin_buffer", C.c_double),
+        ("max_num_cnt", C.c_int),
+        ("first_step", C.c_int),
+        ("last_step", C.c_int),
+        ("evaluator_type", C.c_int),
+        ("longest_valid_segment_length", C.c_double),
+    ]
+
+
 TERM_JOINT_VEL, TERM_JVX, TERM_JPOS, TERM_JDT, TERM_CART, TERM_COLL = range(6)  # thip_term_slot.kind (THIP_TERM_*)
 TERM_KIND_NAMES = ("joint_vel", "jvx", "jpos", "jdt", "cart", "coll")
 # workspace arrays of layout.hpp's DArr / IArr that thip_debug_layout + thip_debug_workspace expose to tests
@@ -547,6 +568,28 @@ def _declare(lib):
     lib.thip_csets_destroy.restype = None
     lib.thip_csets_last_error.argtypes = [vp]
     lib.thip_csets_last_error.restype = C.c_char_p
+    lib.thip_default_ccsets_config.argtypes = [P(CcsetsConfig)]
+    lib.thip_default_ccsets_config.restype = None
+    lib.thip_sizeof_ccsets_config.argtypes = []
+    lib.thip_sizeof_ccsets_config.restype = C.c_int
+    lib.thip_ccsets_create.argtypes = [C.c_int, P(ProblemDesc), P(CcsetsConfig), ip, C.c_int, P(vp)]
+    lib.thip_ccsets_create.restype = C.c_int
+    lib.thip_ccsets_upload.argtypes = [vp, dp]
+    lib.thip_ccsets_upload.restype = C.c_int
+    lib.thip_ccsets_upload_device.argtypes = [vp, vp]
+    lib.thip_ccsets_upload_device.restype = C.c_int
+    lib.thip_ccsets_segments.argtypes = [vp]
+    lib.thip_ccsets_segments.restype = C.c_int
+    lib.thip_ccsets_run.argtypes = [vp, dp, dp, dp, dp, ip, ip]
+    lib.thip_ccsets_run.restype = C.c_int
+    lib.thip_ccsets_run_device.argtypes = [vp, vp, dp, dp, dp, ip, ip]
+    lib.thip_ccsets_run_device.restype = C.c_int
+    lib.thip_ccsets_last_ms.argtypes = [vp]
+    lib.thip_ccsets_last_ms.restype = C.c_double
+    lib.thip_ccsets_destroy.argtypes = [vp]
+    lib.thip_ccsets_destroy.restype = None
+    lib.thip_ccsets_last_error.argtypes = [vp]
+    lib.thip_ccsets_last_error.restype = C.c_char_p
     lib.thip_debug_layout.argtypes = [vp, P(C.c_longlong), P(C.c_longlong), P(C.c_longlong)]
     lib.thip_debug_layout.restype = C.c_int
     lib.thip_debug_workspace.argtypes = [vp, dp, P(C.c_int)]
@@ -623,6 +666,8 @@ def load_hip():
             raise RuntimeError("thip_term_slot layout mismatch between Python and the HIP library")
         if _hip.thip_sizeof_csets_config() != C.sizeof(CsetsConfig):
             raise RuntimeError("thip_csets_config layout mismatch between Python and the HIP library")
+        if _hip.thip_sizeof_ccsets_config() != C.sizeof(CcsetsConfig):
+            raise RuntimeError("thip_ccsets_config layout mismatch between Python and the HIP library")
         if _hip.thip_sizeof_qp_info() != C.sizeof(QpInfo):
             raise RuntimeError("thip_qp_info layout mismatch between Python and the HIP library")
     return _hip

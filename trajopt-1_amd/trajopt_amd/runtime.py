@@ -475,3 +475,82 @@ class CollisionSets:
             self.close()
         except Exception:
             pass
+
+
+class ContinuousCollisionSets:
+    """thip_ccsets_*: the rows of trajopt_ifopt's fixed-size ContinuousCollisionConstraint
+    (LVSContinuousCollisionEvaluator / LVSDiscreteCollisionEvaluator) on every segment
+    (t, t + 1), first_step <= t < last_step, of every problem, one launch per x.  Reads
+    what CollisionSets reads of `desc`; config: abi.CcsetsConfig; scene [B, n_prims, 16];
+    seg_fixed: per segment bit 0 = vars0 fixed, bit 1 = vars1 fixed (None: no end fixed)."""
+
+    def __init__(self, desc, batch, scene, config, seg_fixed=None, device: int = 0):
+        self.lib = abi.load_hip()
+        self.batch = batch
+        self.n_steps, self.n_dof = desc.n_steps, desc.chain.n_dof
+        self.config = config
+        self.cs = C.c_void_p()
+        fixed = None
+        if seg_fixed is not None:
+            fixed = np.ascontiguousarray(seg_fixed, dtype=np.int32)
+            n = config.last_step - config.first_step
+            if fixed.size != max(n, 0) and n > 0:
+                raise HipError(f"ContinuousCollisionSets: seg_fixed has {fixed.size} entries, not {n}")
+        rc = self.lib.thip_ccsets_create(device, C.byref(desc), C.byref(config),
+                                         None if fixed is None else self._ip(fixed), batch, C.byref(self.cs))
+        if rc != 0:
+            raise HipError(f"thip_ccsets_create: {self.lib.thip_ccsets_last_error(None).decode()}")
+        self.n_segments = self.lib.thip_ccsets_segments(self.cs)
+        self.rows = config.max_num_cnt
+        self._scene = np.ascontiguousarray(scene, dtype=np.float64) if desc.n_prims > 0 else None
+        if self._scene is not None and self._scene.size != batch * desc.n_prims * 16:
+            self.close()
+            raise HipError(f"ContinuousCollisionSets: scene has {self._scene.size} values, not [batch][n_prims][16]")
+        self._check(self.lib.thip_ccsets_upload(self.cs, None if self._scene is None else _dp(self._scene)),
+                    "thip_ccsets_upload")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise HipError(f"{what}: {self.lib.thip_ccsets_last_error(self.cs).decode()}")
+
+    def _out(self):
+        B, n, R = self.batch, self.n_segments, self.rows
+        return (np.zeros((B, n, R)), np.zeros((B, n, R, 2, self.n_dof)), np.zeros((B, n, R)),
+                np.zeros((B, n), dtype=np.int32), np.zeros((B, n, R, 4), dtype=np.int32))
+
+    @staticmethod
+    def _ip(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int))
+
+    def run(self, x):
+        """x [B, N, D] (host) -> values [B, n, R], jac [B, n, R, 2, D] (end 0 = node t, end 1 =
+        node t + 1), coeffs [B, n, R], counts [B, n], keys [B, n, R, 4].  Raises when a segment
+        needs more than abi.CCSETS_MAX_SUBSTATES states."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != self.batch * self.n_steps * self.n_dof:
+            raise HipError(f"ContinuousCollisionSets.run: x has {x.size} values, not [batch][n_steps][n_dof]")
+        v, J, cf, cnt, keys = self._out()
+        self._check(self.lib.thip_ccsets_run(self.cs, _dp(x), _dp(v), _dp(J), _dp(cf), self._ip(cnt), self._ip(keys)),
+                    "thip_ccsets_run")
+        return v, J, cf, cnt, keys
+
+    def run_device(self, d_x):
+        """As run() on trajectories already on the device (an address)."""
+        v, J, cf, cnt, keys = self._out()
+        self._check(self.lib.thip_ccsets_run_device(self.cs, C.c_void_p(d_x), _dp(v), _dp(J), _dp(cf), self._ip(cnt),
+                                                    self._ip(keys)), "thip_ccsets_run_device")
+        return v, J, cf, cnt, keys
+
+    def kernel_ms(self) -> float:
+        return float(self.lib.thip_ccsets_last_ms(self.cs))
+
+    def close(self):
+        if self.cs:
+            self.lib.thip_ccsets_destroy(self.cs)
+            self.cs = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -72,10 +72,19 @@ class CollTerm(C.Structure):
                 ("fixed_sparsity", C.c_int), ("margin", C.c_double), ("coeff", C.c_double), ("buffer", C.c_double)]
 
 
+class CcollTerm(C.Structure):
+    """tsqp_ccoll_term: one ContinuousCollisionConstraint per segment of first..last."""
+    _fields_ = [("first", C.c_int), ("last", C.c_int), ("penalty", C.c_int), ("max_num_cnt", C.c_int),
+                ("fixed_sparsity", C.c_int), ("evaluator_type", C.c_int), ("fixed_first", C.c_int),
+                ("fixed_last", C.c_int), ("margin", C.c_double), ("coeff", C.c_double), ("buffer", C.c_double),
+                ("lvs_length", C.c_double)]
+
+
 class KinSpec(C.Structure):
     _fields_ = [("manip", C.c_char * KIN_NAME_LEN), ("n_prims", C.c_int),
                 ("prims", (C.c_double * 16) * KIN_MAX_PRIMS), ("n_cart", C.c_int), ("cart", CartTerm * KIN_MAX_CART),
-                ("n_coll", C.c_int), ("coll", CollTerm * KIN_MAX_COLL)]
+                ("n_coll", C.c_int), ("coll", CollTerm * KIN_MAX_COLL),
+                ("n_ccoll", C.c_int), ("ccoll", CcollTerm * KIN_MAX_COLL)]
 
 
 def _lib():
@@ -90,7 +99,7 @@ def _lib():
                                           C.c_int]
         L.thost_tsqp_eval_kin.restype = C.c_int
         for fn, st in (("thost_tsqp_sizeof_kin_spec", KinSpec), ("thost_tsqp_sizeof_cart_term", CartTerm),
-                       ("thost_tsqp_sizeof_coll_term", CollTerm)):
+                       ("thost_tsqp_sizeof_coll_term", CollTerm), ("thost_tsqp_sizeof_ccoll_term", CcollTerm)):
             getattr(L, fn).restype = C.c_int
             if getattr(L, fn)() != C.sizeof(st):
                 raise RuntimeError(f"{st.__name__} layout mismatch between Python and the host library")
@@ -164,7 +173,7 @@ def solve(spec: Spec, device: int = 0):
     return x, res
 
 
-def make_kin_spec(manip, cart=(), coll=(), prims=None):
+def make_kin_spec(manip, cart=(), coll=(), prims=None, ccoll=()):
     """manip: a group of the built-in environments ("right_arm", "left_arm",
     "both_arms", spherebot's "manipulator").  cart: dicts with node, source_frame,
     target_frame, source_offset / target_offset (12 values, default identity),
@@ -172,8 +181,10 @@ def make_kin_spec(manip, cart=(), coll=(), prims=None):
     analytic_jacobian (use_numeric_differentiation = false: refused).
     coll: dicts with first, last (default first), margin, coeff, buffer,
     max_num_cnt, fixed_sparsity, penalty.  prims [n, 16]: scene primitives added
-    to the environment's own."""
-    if len(cart) > KIN_MAX_CART or len(coll) > KIN_MAX_COLL:
+    to the environment's own.  ccoll: dicts as coll's over the segments of first..last
+    (last > first), plus evaluator_type (tesseract's CollisionEvaluatorType value,
+    default 4 LVS_CONTINUOUS), lvs_length (default 0.005), fixed_first, fixed_last."""
+    if len(cart) > KIN_MAX_CART or len(coll) > KIN_MAX_COLL or len(ccoll) > KIN_MAX_COLL:
         raise ValueError("kinematic spec exceeds TSQP_KIN_MAX_CART / TSQP_KIN_MAX_COLL")
     k = KinSpec()
     k.manip = manip.encode()
@@ -208,6 +219,17 @@ def make_kin_spec(manip, cart=(), coll=(), prims=None):
         T.penalty = int(t.get("penalty", CONSTRAINT))
         T.max_num_cnt, T.fixed_sparsity = int(t.get("max_num_cnt", 3)), int(bool(t.get("fixed_sparsity", True)))
         T.margin, T.coeff, T.buffer = float(t["margin"]), float(t.get("coeff", 1.0)), float(t.get("buffer", 0.01))
+    k.n_ccoll = len(ccoll)
+    for i, t in enumerate(ccoll):
+        T = k.ccoll[i]
+        T.first = int(t.get("first", 0))
+        T.last = int(t.get("last", T.first + 1))
+        T.penalty = int(t.get("penalty", CONSTRAINT))
+        T.max_num_cnt, T.fixed_sparsity = int(t.get("max_num_cnt", 3)), int(bool(t.get("fixed_sparsity", True)))
+        T.evaluator_type = int(t.get("evaluator_type", 4))
+        T.fixed_first, T.fixed_last = int(bool(t.get("fixed_first", False))), int(bool(t.get("fixed_last", False)))
+        T.margin, T.coeff, T.buffer = float(t["margin"]), float(t.get("coeff", 1.0)), float(t.get("buffer", 0.01))
+        T.lvs_length = float(t.get("lvs_length", 0.005))
     return k
 
 
