@@ -35,30 +35,14 @@
 #include <string>
 #include <vector>
 
+#include "coll_sets_common.hpp"
 #include "collision_device.hpp"
-#include "kin_device.hpp"
-#include "pair_data.hpp"
-#include "self_pairs.hpp"
 
 namespace thip
 {
 namespace cs
 {
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kMaxRows = THIP_CSETS_MAX_ROWS;
-constexpr int kLdsPrims = THIP_MAX_PRIMS;  // scenes up to this size are staged in LDS
-
-struct Model
-{
-  int n_sph, n_self_sph;
-  double center[THIP_MAX_SPHERES][3];
-  double radius[THIP_MAX_SPHERES];
-  int link[THIP_MAX_SPHERES];
-  int active[THIP_MAX_LINKS];  // a joint moves the link (getGradient's has_gradient)
-  int self_sa[THIP_MAX_SELF_SPHERE_PAIRS];
-  int self_sb[THIP_MAX_SELF_SPHERE_PAIRS];
-};
+using namespace sets;  // coll_sets_common.hpp: Model, the key packing, the row order
 
 struct Params
 {
@@ -67,35 +51,6 @@ struct Params
   int pw;
   int R, first_step, n_nodes, batch, N, n_prims;
 };
-
-// (link, other, sphere, other_sphere) packed so that unsigned order is the
-// tuple's ascending order: link < 32, other in [-32, 1024), sphere < 32,
-// other_sphere in [-1, 32)
-static_assert(THIP_MAX_LINKS <= 32 && THIP_MAX_SPHERES <= 32 && THIP_EVAL_MAX_PRIMS + 32 <= 2048, "key packing");
-__device__ __forceinline__ unsigned pack_key(int link, int other, int sphere, int osphere)
-{
-  return (static_cast<unsigned>(link) << 22) | (static_cast<unsigned>(other + 32) << 11) |
-         (static_cast<unsigned>(sphere) << 6) | static_cast<unsigned>(osphere + 1);
-}
-__device__ __forceinline__ void unpack_key(unsigned k, int& link, int& other, int& sphere, int& osphere)
-{
-  link = static_cast<int>(k >> 22);
-  other = static_cast<int>((k >> 11) & 2047u) - 32;
-  sphere = static_cast<int>((k >> 6) & 31u);
-  osphere = static_cast<int>(k & 63u) - 1;
-}
-
-// row order: error descending, then the key ascending
-__device__ __forceinline__ bool before(double e, unsigned k, double oe, unsigned ok)
-{
-  return e > oe || (e == oe && k < ok);
-}
-
-__device__ __forceinline__ void sphere_world(const Pose& T, const double* cl, double* c)
-{
-  for (int r = 0; r < 3; ++r)
-    c[r] = T.r[r * 3 + 0] * cl[0] + T.r[r * 3 + 1] * cl[1] + T.r[r * 3 + 2] * cl[2] + T.t[r];
-}
 
 // d(distance)/d(q_j) of one side of a contact: column j of the link's linear
 // jacobian (chain_jacobian's arithmetic over the link poses T) shifted to the
@@ -160,6 +115,7 @@ __global__ __launch_bounds__(kBlock) void csets_kernel(const thip_chain* chain, 
 
   const Model& M = *model;
   const int n_prims = pr.n_prims, R = pr.R;
+  // the prologue (chain and scene to LDS): the same text as ccsets_kernel's, coll_sets_cont.hip
   const double* gprims = scene + static_cast<long long>(b) * (n_prims > 0 ? n_prims : 1) * 16;
   const bool lds_prims = n_prims <= kLdsPrims;
   {
@@ -225,6 +181,8 @@ __global__ __launch_bounds__(kBlock) void csets_kernel(const thip_chain* chain, 
       kept = dist <= margin + pr.buffer;
       err = margin - dist;
     }
+    // the selection step (this compaction, then the ranking below): the same text as ccsets_kernel's,
+    // coll_sets_cont.hip; a change to one is made to both
     const unsigned long long m = __ballot(kept);
     const int lrank = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0)
@@ -343,70 +301,22 @@ __global__ __launch_bounds__(kBlock) void csets_kernel(const thip_chain* chain, 
 
 using namespace thip::cs;
 
-struct thip_csets
+struct thip_csets : thip::sets::Handle
 {
-  int device = 0, batch = 0, D = 0;
   Params pr{};
-  thip_chain* d_chain = nullptr;
-  Model* d_model = nullptr;
-  double* d_pmc = nullptr;
-  double* d_scene = nullptr;
-  double* d_x = nullptr;  // staging of host trajectories
-  double* d_values = nullptr;
-  double* d_jac = nullptr;
-  double* d_coeffs = nullptr;
-  int* d_counts = nullptr;
-  int* d_keys = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool uploaded = false;
-  double last_ms = -1.0;
-  std::string err;
 };
 
 static thread_local std::string g_csets_create_err;
 
-namespace
+static int run_on_device(thip_csets* c, const double* d_x, double* values, double* jac, double* coeffs, int* counts,
+                         int* keys)
 {
-int sfail(thip_csets* c, const std::string& m)
-{
-  c->err = m;
-  return THIP_E_INVALID;
-}
-int shipfail(thip_csets* c, const char* what, hipError_t e)
-{
-  c->err = std::string(what) + ": " + hipGetErrorString(e);
-  return THIP_E_HIP;
-}
-
-int run_on_device(thip_csets* c, const double* d_x, double* values, double* jac, double* coeffs, int* counts, int* keys)
-{
-  const size_t rows = static_cast<size_t>(c->batch) * static_cast<size_t>(c->pr.n_nodes) * static_cast<size_t>(c->pr.R);
-  const size_t items = static_cast<size_t>(c->batch) * static_cast<size_t>(c->pr.n_nodes);
-  hipError_t e;
-  if ((e = hipEventRecord(c->ev0, c->stream)) != hipSuccess)
-    return shipfail(c, "hipEventRecord", e);
-  hipLaunchKernelGGL(csets_kernel, dim3(static_cast<unsigned>(items)), dim3(kBlock), 0, c->stream, c->d_chain,
-                     c->d_model, c->pr, d_x, c->d_scene, c->d_values, c->d_jac, c->d_coeffs, c->d_counts, c->d_keys);
-  if ((e = hipGetLastError()) != hipSuccess)
-    return shipfail(c, "csets_kernel launch", e);
-  if ((e = hipEventRecord(c->ev1, c->stream)) != hipSuccess)
-    return shipfail(c, "hipEventRecord", e);
-  auto back = [&](void* dst, const void* src, size_t bytes) {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  auto launch = [&] {
+    hipLaunchKernelGGL(csets_kernel, dim3(static_cast<unsigned>(c->items)), dim3(kBlock), 0, c->stream, c->d_chain,
+                       c->d_model, c->pr, d_x, c->d_scene, c->d_values, c->d_jac, c->d_coeffs, c->d_counts, c->d_keys);
   };
-  if ((e = back(values, c->d_values, rows * sizeof(double))) != hipSuccess ||
-      (e = back(jac, c->d_jac, rows * static_cast<size_t>(c->D) * sizeof(double))) != hipSuccess ||
-      (e = back(coeffs, c->d_coeffs, rows * sizeof(double))) != hipSuccess ||
-      (e = back(counts, c->d_counts, items * sizeof(int))) != hipSuccess ||
-      (e = back(keys, c->d_keys, rows * 4 * sizeof(int))) != hipSuccess ||
-      (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-    return shipfail(c, "csets_kernel", e);
-  float ms = -1.0f;
-  c->last_ms = hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess ? static_cast<double>(ms) : -1.0;
-  return THIP_OK;
+  return launch_and_fetch(c, "csets_kernel", launch, values, jac, coeffs, counts, keys);
 }
-}  // namespace
 
 extern "C" {
 
@@ -434,52 +344,14 @@ int thip_csets_create(int device, const thip_problem_desc* desc, const thip_cset
     g_csets_create_err = "thip_csets_create: null argument or batch <= 0";
     return THIP_E_INVALID;
   }
-  auto reject = [](const std::string& m) {
+  const Reject reject = [](const std::string& m) {
     g_csets_create_err = "thip_csets_create: " + m;
     return THIP_E_INVALID;
   };
-  if (desc->abi_version != THIP_ABI_VERSION)
-    return reject("descriptor abi_version " + std::to_string(desc->abi_version) + " != THIP_ABI_VERSION " +
-                  std::to_string(THIP_ABI_VERSION));
-  const thip_chain& ch = desc->chain;
-  const int N = desc->n_steps;
-  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF || ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
-    return reject("chain out of range");
-  for (int k = 1; k < ch.n_links; ++k)
-    if ((ch.joint_type[k] < 0 || ch.joint_type[k] > 3) ||
-        (ch.joint_type[k] != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof)) ||
-        (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k)))
-      return reject("bad chain joint / parent table");
-  if (N < 1 || N > THIP_EVAL_MAX_STEPS)
-    return reject("n_steps out of range");
-  if (desc->n_prims < 0 || desc->n_prims > THIP_EVAL_MAX_PRIMS)
-    return reject("n_prims out of range");
-  if (desc->n_spheres == 0)
-    return reject("the descriptor has no robot spheres: collision sets need the robot's sphere model "
-                  "(n_spheres / sphere_link / sphere_center / sphere_radius)");
-  if (desc->n_spheres < 0 || desc->n_spheres > THIP_MAX_SPHERES)
-    return reject("n_spheres out of range");
-  for (int s = 0; s < desc->n_spheres; ++s)
-  {
-    if (desc->sphere_link[s] < 1 || desc->sphere_link[s] >= ch.n_links)
-      return reject("bad sphere link of robot sphere " + std::to_string(s));
-    if (!(desc->sphere_radius[s] >= 0) || !std::isfinite(desc->sphere_radius[s]))
-      return reject("bad sphere radius of robot sphere " + std::to_string(s));
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(desc->sphere_center[s][i]))
-        return reject("bad sphere center of robot sphere " + std::to_string(s));
-  }
-  if (!std::isfinite(cfg->margin))
-    return reject("margin is not finite");
-  if (!std::isfinite(cfg->coeff))
-    return reject("coeff is not finite");
-  if (!std::isfinite(cfg->margin_buffer))
-    return reject("margin_buffer is not finite");
-  if (cfg->max_num_cnt < 1 || cfg->max_num_cnt > THIP_CSETS_MAX_ROWS)
-    return reject("max_num_cnt " + std::to_string(cfg->max_num_cnt) + " out of range [1, " +
-                  std::to_string(THIP_CSETS_MAX_ROWS) + "]");
+  if (check_descriptor(*desc, *cfg, reject) != THIP_OK)
+    return THIP_E_INVALID;
   // each bound on its own: no sum or difference of caller values before they are known to lie in [0, N)
-  const int first = cfg->first_step, last = cfg->last_step;
+  const int N = desc->n_steps, first = cfg->first_step, last = cfg->last_step;
   if (first < 0 || first >= N || last < 0 || last >= N)
     return reject("step range [" + std::to_string(first) + ", " + std::to_string(last) + "] outside [0, " +
                   std::to_string(N - 1) + "]");
@@ -488,59 +360,15 @@ int thip_csets_create(int device, const thip_problem_desc* desc, const thip_cset
   const int n_nodes = last - first + 1;
   if (static_cast<long long>(n_nodes) * batch > INT_MAX / (THIP_CSETS_MAX_ROWS * 4))
     return reject("batch * nodes exceeds the grid");
-  if (desc->n_coll_pairs < 0 || desc->n_coll_pairs > THIP_MAX_COLL_PAIRS)
-    return reject("n_coll_pairs out of range");
-  for (int k = 0; k < desc->n_coll_pairs; ++k)
-  {
-    const thip_coll_pair& e = desc->coll_pairs[k];
-    if (e.term != 0)
-      continue;  // another term's override: not read
-    if (e.link < 0 || e.link >= ch.n_links)
-      return reject("coll_pairs[" + std::to_string(k) + "].link out of range");
-    if (e.other >= 0 ? e.other >= desc->n_prims : (e.other < -ch.n_links))
-      return reject("coll_pairs[" + std::to_string(k) + "].other out of range");
-    if (!std::isfinite(e.margin) || !std::isfinite(e.coeff))
-      return reject("coll_pairs[" + std::to_string(k) + "] margin / coeff must be finite");
-  }
-  std::vector<int> ssa, ssb, skp;
-  {
-    const std::string why = thip::self_sphere_pairs(*desc, ssa, ssb, skp);
-    if (!why.empty())
-      return reject(why);
-  }
-  // the selection needs unique keys: a link pair listed twice, in either
-  // order, would put the same contacts into the pool twice
-  for (int k = 1; k < desc->n_self_pairs; ++k)
-    for (int o = 0; o < k; ++o)
-    {
-      const int a = desc->self_pair[k][0], b = desc->self_pair[k][1];
-      const int oa = desc->self_pair[o][0], ob = desc->self_pair[o][1];
-      if ((a == oa && b == ob) || (a == ob && b == oa))
-        return reject("self_pair[" + std::to_string(k) + "] repeats self_pair[" + std::to_string(o) +
-                      "]: each link pair may be listed once");
-    }
-  // term 0's overrides over the config's margin and coefficient (pair_data.hpp)
+  std::vector<int> ssa, ssb;
   std::vector<double> tab;
-  {
-    std::unique_ptr<thip_problem_desc> d2(new thip_problem_desc(*desc));
-    d2->coll_enabled = 1;
-    d2->coll_margin = cfg->margin;
-    d2->coll_coeff = cfg->coeff;
-    d2->n_coll_pairs = 0;
-    for (int k = 0; k < desc->n_coll_pairs; ++k)
-      if (desc->coll_pairs[k].term == 0)
-        d2->coll_pairs[d2->n_coll_pairs++] = desc->coll_pairs[k];
-    thip::coll_pair_table(*d2, 0, tab);
-  }
+  if (check_pairs(*desc, cfg->margin, cfg->coeff, reject, ssa, ssb, tab) != THIP_OK)
+    return THIP_E_INVALID;
 
   auto* c = new thip_csets();
-  c->device = device;
-  c->batch = batch;
-  c->D = ch.n_dof;
   c->pr.margin = cfg->margin;
   c->pr.coeff = cfg->coeff;
   c->pr.buffer = cfg->margin_buffer;
-  c->pr.pmc = nullptr;
   c->pr.pw = desc->n_prims + desc->n_spheres;
   c->pr.R = cfg->max_num_cnt;
   c->pr.first_step = first;
@@ -548,93 +376,30 @@ int thip_csets_create(int device, const thip_problem_desc* desc, const thip_cset
   c->pr.batch = batch;
   c->pr.N = N;
   c->pr.n_prims = desc->n_prims;
-  thip_chain chain = ch;
-  if (!chain.is_tree)
-    for (int k = 0; k < THIP_MAX_LINKS; ++k)
-      chain.parent[k] = k > 0 ? k - 1 : 0;
+  thip_chain chain;
   std::unique_ptr<Model> md(new Model());
-  md->n_sph = desc->n_spheres;
-  md->n_self_sph = static_cast<int>(ssa.size());
-  for (size_t j = 0; j < ssa.size(); ++j)
+  fill_model(*desc, ssa, ssb, chain, *md);
+  const std::string why = allocate_and_upload(*c, device, batch, *desc, static_cast<size_t>(batch) * n_nodes,
+                                              cfg->max_num_cnt, desc->chain.n_dof, chain, *md, tab);
+  if (!why.empty())
   {
-    md->self_sa[j] = ssa[j];
-    md->self_sb[j] = ssb[j];
-  }
-  for (int s = 0; s < desc->n_spheres; ++s)
-  {
-    md->link[s] = desc->sphere_link[s];
-    md->radius[s] = desc->sphere_radius[s];
-    for (int i = 0; i < 3; ++i)
-      md->center[s][i] = desc->sphere_center[s][i];
-  }
-  for (int k = 1; k < chain.n_links; ++k)
-    md->active[k] = (chain.joint_type[k] != THIP_JOINT_FIXED || md->active[chain.parent[k]]) ? 1 : 0;
-
-  auto hfail = [&](const char* what, hipError_t e) {
-    g_csets_create_err = std::string("thip_csets_create: ") + what + ": " + hipGetErrorString(e);
+    g_csets_create_err = "thip_csets_create: " + why;
     thip_csets_destroy(c);
     return THIP_E_HIP;
-  };
-  hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess)
-    return hfail("hipSetDevice", e);
-  const size_t B = static_cast<size_t>(batch), items = B * static_cast<size_t>(n_nodes);
-  const size_t rows = items * static_cast<size_t>(c->pr.R);
-  const size_t np = static_cast<size_t>(std::max(desc->n_prims, 1));
-  if ((e = hipMalloc(&c->d_chain, sizeof(thip_chain))) != hipSuccess ||
-      (e = hipMalloc(&c->d_model, sizeof(Model))) != hipSuccess ||
-      (e = hipMalloc(&c->d_scene, B * np * 16 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_x, B * static_cast<size_t>(N) * c->D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_values, rows * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_jac, rows * c->D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_coeffs, rows * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_counts, items * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc(&c->d_keys, rows * 4 * sizeof(int))) != hipSuccess ||
-      (!tab.empty() && (e = hipMalloc(&c->d_pmc, tab.size() * sizeof(double))) != hipSuccess))
-    return hfail("hipMalloc", e);
+  }
   c->pr.pmc = c->d_pmc;
-  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
-    return hfail("hipStreamCreate", e);
-  if ((e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess)
-    return hfail("hipEventCreate", e);
-  if ((e = hipMemcpyAsync(c->d_chain, &chain, sizeof(thip_chain), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(c->d_model, md.get(), sizeof(Model), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-      (!tab.empty() && (e = hipMemcpyAsync(c->d_pmc, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice,
-                                           c->stream)) != hipSuccess) ||
-      (e = hipMemsetAsync(c->d_scene, 0, B * np * 16 * sizeof(double), c->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-    return hfail("hipMemcpy", e);
   *out = c;
-  return THIP_OK;
-}
-
-static int csets_upload_scene(thip_csets* c, const double* scene, hipMemcpyKind kind, const char* who)
-{
-  if (!c)
-    return THIP_E_INVALID;
-  if (c->pr.n_prims > 0 && !scene)
-    return sfail(c, std::string(who) + ": scene required when n_prims > 0");
-  hipError_t e;
-  if ((e = hipSetDevice(c->device)) != hipSuccess)
-    return shipfail(c, "hipSetDevice", e);
-  if (c->pr.n_prims > 0 &&
-      ((e = hipMemcpyAsync(c->d_scene, scene,
-                           static_cast<size_t>(c->batch) * static_cast<size_t>(c->pr.n_prims) * 16 * sizeof(double), kind,
-                           c->stream)) != hipSuccess ||
-       (e = hipStreamSynchronize(c->stream)) != hipSuccess))
-    return shipfail(c, "hipMemcpy(scene)", e);
-  c->uploaded = true;
   return THIP_OK;
 }
 
 int thip_csets_upload(thip_csets* cs, const double* scene)
 {
-  return csets_upload_scene(cs, scene, hipMemcpyHostToDevice, "thip_csets_upload");
+  return upload_scene(cs, scene, hipMemcpyHostToDevice, "thip_csets_upload");
 }
 
 int thip_csets_upload_device(thip_csets* cs, const double* d_scene)
 {
-  return csets_upload_scene(cs, d_scene, hipMemcpyDeviceToDevice, "thip_csets_upload_device");
+  return upload_scene(cs, d_scene, hipMemcpyDeviceToDevice, "thip_csets_upload_device");
 }
 
 int thip_csets_nodes(const thip_csets* cs) { return cs ? cs->pr.n_nodes : THIP_E_INVALID; }
@@ -642,35 +407,16 @@ int thip_csets_nodes(const thip_csets* cs) { return cs ? cs->pr.n_nodes : THIP_E
 int thip_csets_run(thip_csets* cs, const double* x, double* values, double* jac, double* coeffs, int* counts,
                    int* keys)
 {
-  if (!cs)
-    return THIP_E_INVALID;
-  if (!x)
-    return sfail(cs, "thip_csets_run: null x");
-  if (!cs->uploaded)
-    return sfail(cs, "thip_csets_run: thip_csets_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(cs->device)) != hipSuccess)
-    return shipfail(cs, "hipSetDevice", e);
-  if ((e = hipMemcpyAsync(cs->d_x, x,
-                          static_cast<size_t>(cs->batch) * static_cast<size_t>(cs->pr.N) * cs->D * sizeof(double),
-                          hipMemcpyHostToDevice, cs->stream)) != hipSuccess)
-    return shipfail(cs, "hipMemcpy(x)", e);
-  return run_on_device(cs, cs->d_x, values, jac, coeffs, counts, keys);
+  const double* d_x = nullptr;
+  const int rc = stage_x(cs, "thip_csets", x, true, d_x);
+  return rc != THIP_OK ? rc : run_on_device(cs, d_x, values, jac, coeffs, counts, keys);
 }
 
 int thip_csets_run_device(thip_csets* cs, const double* d_x, double* values, double* jac, double* coeffs, int* counts,
                           int* keys)
 {
-  if (!cs)
-    return THIP_E_INVALID;
-  if (!d_x)
-    return sfail(cs, "thip_csets_run_device: null d_x");
-  if (!cs->uploaded)
-    return sfail(cs, "thip_csets_run_device: thip_csets_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(cs->device)) != hipSuccess)
-    return shipfail(cs, "hipSetDevice", e);
-  return run_on_device(cs, d_x, values, jac, coeffs, counts, keys);
+  const int rc = stage_x(cs, "thip_csets", d_x, false, d_x);
+  return rc != THIP_OK ? rc : run_on_device(cs, d_x, values, jac, coeffs, counts, keys);
 }
 
 double thip_csets_last_ms(thip_csets* cs) { return cs ? cs->last_ms : -1.0; }
@@ -679,25 +425,7 @@ void thip_csets_destroy(thip_csets* cs)
 {
   if (!cs)
     return;
-  hipSetDevice(cs->device);
-  if (cs->stream)
-    hipStreamSynchronize(cs->stream);
-  hipFree(cs->d_chain);
-  hipFree(cs->d_model);
-  hipFree(cs->d_pmc);
-  hipFree(cs->d_scene);
-  hipFree(cs->d_x);
-  hipFree(cs->d_values);
-  hipFree(cs->d_jac);
-  hipFree(cs->d_coeffs);
-  hipFree(cs->d_counts);
-  hipFree(cs->d_keys);
-  if (cs->ev0)
-    hipEventDestroy(cs->ev0);
-  if (cs->ev1)
-    hipEventDestroy(cs->ev1);
-  if (cs->stream)
-    hipStreamDestroy(cs->stream);
+  release(cs);
   delete cs;
 }
 

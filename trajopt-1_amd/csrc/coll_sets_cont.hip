@@ -46,32 +46,17 @@
 #include <string>
 #include <vector>
 
+#include "coll_sets_common.hpp"
 #include "collision_device.hpp"
-#include "kin_device.hpp"
-#include "pair_data.hpp"
-#include "self_pairs.hpp"
 
 namespace thip
 {
 namespace ccs
 {
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kMaxRows = THIP_CSETS_MAX_ROWS;
-constexpr int kLdsPrims = THIP_MAX_PRIMS;  // scenes up to this size are staged in LDS
+using namespace sets;  // coll_sets_common.hpp: Model, the key packing, the row order
+
 constexpr int kMaxStates = THIP_CCSETS_MAX_SUBSTATES;
 constexpr int kCCNone = 0, kCCTime0 = 1, kCCTime1 = 2, kCCBetween = 3;
-
-struct Model
-{
-  int n_sph, n_self_sph;
-  double center[THIP_MAX_SPHERES][3];
-  double radius[THIP_MAX_SPHERES];
-  int link[THIP_MAX_SPHERES];
-  int active[THIP_MAX_LINKS];  // a joint moves the link (getGradient's isActiveLinkId)
-  int self_sa[THIP_MAX_SELF_SPHERE_PAIRS];
-  int self_sb[THIP_MAX_SELF_SPHERE_PAIRS];
-};
 
 struct Params
 {
@@ -83,33 +68,6 @@ struct Params
   int cast;     // CONTINUOUS / LVS_CONTINUOUS: casts between consecutive states
   int one_cast; // CONTINUOUS: two states whatever the joint distance
 };
-
-// coll_sets.hip's key packing: unsigned order is the tuple's ascending order
-static_assert(THIP_MAX_LINKS <= 32 && THIP_MAX_SPHERES <= 32 && THIP_EVAL_MAX_PRIMS + 32 <= 2048, "key packing");
-__device__ __forceinline__ unsigned pack_key(int link, int other, int sphere, int osphere)
-{
-  return (static_cast<unsigned>(link) << 22) | (static_cast<unsigned>(other + 32) << 11) |
-         (static_cast<unsigned>(sphere) << 6) | static_cast<unsigned>(osphere + 1);
-}
-__device__ __forceinline__ void unpack_key(unsigned k, int& link, int& other, int& sphere, int& osphere)
-{
-  link = static_cast<int>(k >> 22);
-  other = static_cast<int>((k >> 11) & 2047u) - 32;
-  sphere = static_cast<int>((k >> 6) & 31u);
-  osphere = static_cast<int>(k & 63u) - 1;
-}
-
-// row order: E descending, then the key ascending
-__device__ __forceinline__ bool before(double e, unsigned k, double oe, unsigned ok)
-{
-  return e > oe || (e == oe && k < ok);
-}
-
-__device__ __forceinline__ void sphere_world(const Pose& T, const double* cl, double* c)
-{
-  for (int r = 0; r < 3; ++r)
-    c[r] = T.r[r * 3 + 0] * cl[0] + T.r[r * 3 + 1] * cl[1] + T.r[r * 3 + 2] * cl[2] + T.t[r];
-}
 
 struct Contact
 {
@@ -280,6 +238,7 @@ __global__ __launch_bounds__(kBlock) void ccsets_kernel(const thip_chain* chain,
 
   const Model& M = *model;
   const int n_prims = pr.n_prims, R = pr.R;
+  // the prologue (chain and scene to LDS): the same text as csets_kernel's, coll_sets.hip
   const double* gprims = scene + static_cast<long long>(b) * (n_prims > 0 ? n_prims : 1) * 16;
   const bool lds_prims = n_prims <= kLdsPrims;
   {
@@ -433,6 +392,8 @@ __global__ __launch_bounds__(kBlock) void ccsets_kernel(const thip_chain* chain,
     // getMaxError / getMaxErrorT0 / getMaxErrorT1; -inf: no error at the free end
     const double E = f1 ? fmax(m00, m10) : (f0 ? fmax(m01, m11) : fmax(fmax(m00, m01), fmax(m10, m11)));
     __syncthreads();  // the last sub-state's reads; s_wcnt and the pass arrays of the previous pass
+    // the selection step (this compaction, then the ranking below): the same text as csets_kernel's,
+    // coll_sets.hip; a change to one is made to both
     const unsigned long long mk = __ballot(any);
     const int lrank = __popcll(mk & ((1ull << lane) - 1ull));
     if (lane == 0)
@@ -586,81 +547,35 @@ __global__ __launch_bounds__(kBlock) void ccsets_kernel(const thip_chain* chain,
 
 using namespace thip::ccs;
 
-struct thip_ccsets
+struct thip_ccsets : thip::sets::Handle
 {
-  int device = 0, batch = 0, D = 0;
   Params pr{};
-  thip_chain* d_chain = nullptr;
-  Model* d_model = nullptr;
-  double* d_pmc = nullptr;
   int* d_fixed = nullptr;
-  double* d_scene = nullptr;
-  double* d_x = nullptr;  // staging of host trajectories
-  double* d_values = nullptr;
-  double* d_jac = nullptr;
-  double* d_coeffs = nullptr;
-  int* d_counts = nullptr;
-  int* d_keys = nullptr;
   std::vector<int> h_counts;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool uploaded = false;
-  double last_ms = -1.0;
-  std::string err;
 };
 
 static thread_local std::string g_ccsets_create_err;
 
-namespace
+static int run_on_device(thip_ccsets* c, const double* d_x, double* values, double* jac, double* coeffs, int* counts,
+                         int* keys)
 {
-int sfail(thip_ccsets* c, const std::string& m)
-{
-  c->err = m;
-  return THIP_E_INVALID;
-}
-int shipfail(thip_ccsets* c, const char* what, hipError_t e)
-{
-  c->err = std::string(what) + ": " + hipGetErrorString(e);
-  return THIP_E_HIP;
-}
-
-int run_on_device(thip_ccsets* c, const double* d_x, double* values, double* jac, double* coeffs, int* counts,
-                  int* keys)
-{
-  const size_t items = static_cast<size_t>(c->batch) * static_cast<size_t>(c->pr.n_seg);
-  const size_t rows = items * static_cast<size_t>(c->pr.R);
-  hipError_t e;
-  if ((e = hipEventRecord(c->ev0, c->stream)) != hipSuccess)
-    return shipfail(c, "hipEventRecord", e);
-  hipLaunchKernelGGL(ccsets_kernel, dim3(static_cast<unsigned>(items)), dim3(kBlock), 0, c->stream, c->d_chain,
-                     c->d_model, c->pr, d_x, c->d_scene, c->d_values, c->d_jac, c->d_coeffs, c->d_counts, c->d_keys);
-  if ((e = hipGetLastError()) != hipSuccess)
-    return shipfail(c, "ccsets_kernel launch", e);
-  if ((e = hipEventRecord(c->ev1, c->stream)) != hipSuccess)
-    return shipfail(c, "hipEventRecord", e);
-  auto back = [&](void* dst, const void* src, size_t bytes) {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  auto launch = [&] {
+    hipLaunchKernelGGL(ccsets_kernel, dim3(static_cast<unsigned>(c->items)), dim3(kBlock), 0, c->stream, c->d_chain,
+                       c->d_model, c->pr, d_x, c->d_scene, c->d_values, c->d_jac, c->d_coeffs, c->d_counts, c->d_keys);
   };
-  if ((e = back(values, c->d_values, rows * sizeof(double))) != hipSuccess ||
-      (e = back(jac, c->d_jac, rows * 2 * static_cast<size_t>(c->D) * sizeof(double))) != hipSuccess ||
-      (e = back(coeffs, c->d_coeffs, rows * sizeof(double))) != hipSuccess ||
-      (e = back(c->h_counts.data(), c->d_counts, items * sizeof(int))) != hipSuccess ||
-      (e = back(keys, c->d_keys, rows * 4 * sizeof(int))) != hipSuccess ||
-      (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-    return shipfail(c, "ccsets_kernel", e);
-  float ms = -1.0f;
-  c->last_ms = hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess ? static_cast<double>(ms) : -1.0;
+  const int rc = launch_and_fetch(c, "ccsets_kernel", launch, values, jac, coeffs, c->h_counts.data(), keys);
+  if (rc != THIP_OK)
+    return rc;
   if (counts)
     std::copy(c->h_counts.begin(), c->h_counts.end(), counts);
-  for (size_t it = 0; it < items; ++it)
+  for (size_t it = 0; it < c->items; ++it)
     if (c->h_counts[it] < 0)
-      return sfail(c, "thip_ccsets_run: problem " + std::to_string(it / static_cast<size_t>(c->pr.n_seg)) +
-                          " segment " + std::to_string(it % static_cast<size_t>(c->pr.n_seg)) + " needs more than " +
-                          std::to_string(THIP_CCSETS_MAX_SUBSTATES) +
-                          " sub-states (THIP_CCSETS_MAX_SUBSTATES): its rows are padded");
+      return fail(c, "thip_ccsets_run: problem " + std::to_string(it / static_cast<size_t>(c->pr.n_seg)) +
+                         " segment " + std::to_string(it % static_cast<size_t>(c->pr.n_seg)) + " needs more than " +
+                         std::to_string(THIP_CCSETS_MAX_SUBSTATES) +
+                         " sub-states (THIP_CCSETS_MAX_SUBSTATES): its rows are padded");
   return THIP_OK;
 }
-}  // namespace
 
 extern "C" {
 
@@ -690,50 +605,12 @@ int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccs
     g_ccsets_create_err = "thip_ccsets_create: null argument or batch <= 0";
     return THIP_E_INVALID;
   }
-  auto reject = [](const std::string& m) {
+  const Reject reject = [](const std::string& m) {
     g_ccsets_create_err = "thip_ccsets_create: " + m;
     return THIP_E_INVALID;
   };
-  if (desc->abi_version != THIP_ABI_VERSION)
-    return reject("descriptor abi_version " + std::to_string(desc->abi_version) + " != THIP_ABI_VERSION " +
-                  std::to_string(THIP_ABI_VERSION));
-  const thip_chain& ch = desc->chain;
-  const int N = desc->n_steps;
-  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF || ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
-    return reject("chain out of range");
-  for (int k = 1; k < ch.n_links; ++k)
-    if ((ch.joint_type[k] < 0 || ch.joint_type[k] > 3) ||
-        (ch.joint_type[k] != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof)) ||
-        (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k)))
-      return reject("bad chain joint / parent table");
-  if (N < 1 || N > THIP_EVAL_MAX_STEPS)
-    return reject("n_steps out of range");
-  if (desc->n_prims < 0 || desc->n_prims > THIP_EVAL_MAX_PRIMS)
-    return reject("n_prims out of range");
-  if (desc->n_spheres == 0)
-    return reject("the descriptor has no robot spheres: collision sets need the robot's sphere model "
-                  "(n_spheres / sphere_link / sphere_center / sphere_radius)");
-  if (desc->n_spheres < 0 || desc->n_spheres > THIP_MAX_SPHERES)
-    return reject("n_spheres out of range");
-  for (int s = 0; s < desc->n_spheres; ++s)
-  {
-    if (desc->sphere_link[s] < 1 || desc->sphere_link[s] >= ch.n_links)
-      return reject("bad sphere link of robot sphere " + std::to_string(s));
-    if (!(desc->sphere_radius[s] >= 0) || !std::isfinite(desc->sphere_radius[s]))
-      return reject("bad sphere radius of robot sphere " + std::to_string(s));
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(desc->sphere_center[s][i]))
-        return reject("bad sphere center of robot sphere " + std::to_string(s));
-  }
-  if (!std::isfinite(cfg->margin))
-    return reject("margin is not finite");
-  if (!std::isfinite(cfg->coeff))
-    return reject("coeff is not finite");
-  if (!std::isfinite(cfg->margin_buffer))
-    return reject("margin_buffer is not finite");
-  if (cfg->max_num_cnt < 1 || cfg->max_num_cnt > THIP_CSETS_MAX_ROWS)
-    return reject("max_num_cnt " + std::to_string(cfg->max_num_cnt) + " out of range [1, " +
-                  std::to_string(THIP_CSETS_MAX_ROWS) + "]");
+  if (check_descriptor(*desc, *cfg, reject) != THIP_OK)
+    return THIP_E_INVALID;
   const int et = cfg->evaluator_type;
   if (et != THIP_EVALUATOR_LVS_DISCRETE && et != THIP_EVALUATOR_CONTINUOUS && et != THIP_EVALUATOR_LVS_CONTINUOUS)
     return reject("evaluator_type " + std::to_string(et) +
@@ -741,7 +618,7 @@ int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccs
   if (!std::isfinite(cfg->longest_valid_segment_length) || !(cfg->longest_valid_segment_length > 0))
     return reject("longest_valid_segment_length must be finite and > 0");
   // each bound on its own: no sum or difference of caller values before they are known to lie in [0, N)
-  const int first = cfg->first_step, last = cfg->last_step;
+  const int N = desc->n_steps, first = cfg->first_step, last = cfg->last_step;
   if (first < 0 || first >= N || last < 0 || last >= N)
     return reject("step range [" + std::to_string(first) + ", " + std::to_string(last) + "] outside [0, " +
                   std::to_string(N - 1) + "]");
@@ -758,61 +635,16 @@ int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccs
     if (seg_fixed[k] == 3)
       return reject("seg_fixed[" + std::to_string(k) + "]: both ends cannot be fixed!");
   }
-  if (desc->n_coll_pairs < 0 || desc->n_coll_pairs > THIP_MAX_COLL_PAIRS)
-    return reject("n_coll_pairs out of range");
-  for (int k = 0; k < desc->n_coll_pairs; ++k)
-  {
-    const thip_coll_pair& e = desc->coll_pairs[k];
-    if (e.term != 0)
-      continue;  // another term's override: not read
-    if (e.link < 0 || e.link >= ch.n_links)
-      return reject("coll_pairs[" + std::to_string(k) + "].link out of range");
-    if (e.other >= 0 ? e.other >= desc->n_prims : (e.other < -ch.n_links))
-      return reject("coll_pairs[" + std::to_string(k) + "].other out of range");
-    if (!std::isfinite(e.margin) || !std::isfinite(e.coeff))
-      return reject("coll_pairs[" + std::to_string(k) + "] margin / coeff must be finite");
-  }
-  std::vector<int> ssa, ssb, skp;
-  {
-    const std::string why = thip::self_sphere_pairs(*desc, ssa, ssb, skp);
-    if (!why.empty())
-      return reject(why);
-  }
-  // the selection needs unique keys: a link pair listed twice, in either
-  // order, would put the same sets into the pool twice
-  for (int k = 1; k < desc->n_self_pairs; ++k)
-    for (int o = 0; o < k; ++o)
-    {
-      const int a = desc->self_pair[k][0], b = desc->self_pair[k][1];
-      const int oa = desc->self_pair[o][0], ob = desc->self_pair[o][1];
-      if ((a == oa && b == ob) || (a == ob && b == oa))
-        return reject("self_pair[" + std::to_string(k) + "] repeats self_pair[" + std::to_string(o) +
-                      "]: each link pair may be listed once");
-    }
-  // term 0's overrides over the config's margin and coefficient (pair_data.hpp)
+  std::vector<int> ssa, ssb;
   std::vector<double> tab;
-  {
-    std::unique_ptr<thip_problem_desc> d2(new thip_problem_desc(*desc));
-    d2->coll_enabled = 1;
-    d2->coll_margin = cfg->margin;
-    d2->coll_coeff = cfg->coeff;
-    d2->n_coll_pairs = 0;
-    for (int k = 0; k < desc->n_coll_pairs; ++k)
-      if (desc->coll_pairs[k].term == 0)
-        d2->coll_pairs[d2->n_coll_pairs++] = desc->coll_pairs[k];
-    thip::coll_pair_table(*d2, 0, tab);
-  }
+  if (check_pairs(*desc, cfg->margin, cfg->coeff, reject, ssa, ssb, tab) != THIP_OK)
+    return THIP_E_INVALID;
 
   auto* c = new thip_ccsets();
-  c->device = device;
-  c->batch = batch;
-  c->D = ch.n_dof;
   c->pr.margin = cfg->margin;
   c->pr.coeff = cfg->coeff;
   c->pr.buffer = cfg->margin_buffer;
   c->pr.lvs = cfg->longest_valid_segment_length;
-  c->pr.pmc = nullptr;
-  c->pr.seg_fixed = nullptr;
   c->pr.pw = desc->n_prims + desc->n_spheres;
   c->pr.R = cfg->max_num_cnt;
   c->pr.first_step = first;
@@ -822,101 +654,42 @@ int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccs
   c->pr.n_prims = desc->n_prims;
   c->pr.cast = et != THIP_EVALUATOR_LVS_DISCRETE ? 1 : 0;
   c->pr.one_cast = et == THIP_EVALUATOR_CONTINUOUS ? 1 : 0;
-  c->h_counts.assign(static_cast<size_t>(batch) * static_cast<size_t>(n_seg), 0);
-  thip_chain chain = ch;
-  if (!chain.is_tree)
-    for (int k = 0; k < THIP_MAX_LINKS; ++k)
-      chain.parent[k] = k > 0 ? k - 1 : 0;
+  c->h_counts.assign(static_cast<size_t>(batch) * n_seg, 0);
+  thip_chain chain;
   std::unique_ptr<Model> md(new Model());
-  md->n_sph = desc->n_spheres;
-  md->n_self_sph = static_cast<int>(ssa.size());
-  for (size_t j = 0; j < ssa.size(); ++j)
-  {
-    md->self_sa[j] = ssa[j];
-    md->self_sb[j] = ssb[j];
-  }
-  for (int s = 0; s < desc->n_spheres; ++s)
-  {
-    md->link[s] = desc->sphere_link[s];
-    md->radius[s] = desc->sphere_radius[s];
-    for (int i = 0; i < 3; ++i)
-      md->center[s][i] = desc->sphere_center[s][i];
-  }
-  for (int k = 1; k < chain.n_links; ++k)
-    md->active[k] = (chain.joint_type[k] != THIP_JOINT_FIXED || md->active[chain.parent[k]]) ? 1 : 0;
+  fill_model(*desc, ssa, ssb, chain, *md);
   std::vector<int> fixed(static_cast<size_t>(n_seg), 0);
   for (int k = 0; seg_fixed && k < n_seg; ++k)
     fixed[k] = seg_fixed[k];
 
-  auto hfail = [&](const char* what, hipError_t e) {
-    g_ccsets_create_err = std::string("thip_ccsets_create: ") + what + ": " + hipGetErrorString(e);
+  auto hfail = [&](const std::string& why) {
+    g_ccsets_create_err = "thip_ccsets_create: " + why;
     thip_ccsets_destroy(c);
     return THIP_E_HIP;
   };
+  const std::string why = allocate_and_upload(*c, device, batch, *desc, static_cast<size_t>(batch) * n_seg,
+                                              cfg->max_num_cnt, 2 * desc->chain.n_dof, chain, *md, tab);
+  if (!why.empty())
+    return hfail(why);
   hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess)
-    return hfail("hipSetDevice", e);
-  const size_t B = static_cast<size_t>(batch), items = B * static_cast<size_t>(n_seg);
-  const size_t rows = items * static_cast<size_t>(c->pr.R);
-  const size_t np = static_cast<size_t>(std::max(desc->n_prims, 1));
-  if ((e = hipMalloc(&c->d_chain, sizeof(thip_chain))) != hipSuccess ||
-      (e = hipMalloc(&c->d_model, sizeof(Model))) != hipSuccess ||
-      (e = hipMalloc(&c->d_fixed, fixed.size() * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc(&c->d_scene, B * np * 16 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_x, B * static_cast<size_t>(N) * c->D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_values, rows * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_jac, rows * 2 * c->D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_coeffs, rows * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_counts, items * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc(&c->d_keys, rows * 4 * sizeof(int))) != hipSuccess ||
-      (!tab.empty() && (e = hipMalloc(&c->d_pmc, tab.size() * sizeof(double))) != hipSuccess))
-    return hfail("hipMalloc", e);
+  if ((e = hipMalloc(&c->d_fixed, fixed.size() * sizeof(int))) != hipSuccess)
+    return hfail(std::string("hipMalloc: ") + hipGetErrorString(e));
+  if ((e = hipMemcpy(c->d_fixed, fixed.data(), fixed.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
+    return hfail(std::string("hipMemcpy: ") + hipGetErrorString(e));
   c->pr.pmc = c->d_pmc;
   c->pr.seg_fixed = c->d_fixed;
-  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
-    return hfail("hipStreamCreate", e);
-  if ((e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess)
-    return hfail("hipEventCreate", e);
-  if ((e = hipMemcpyAsync(c->d_chain, &chain, sizeof(thip_chain), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(c->d_model, md.get(), sizeof(Model), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(c->d_fixed, fixed.data(), fixed.size() * sizeof(int), hipMemcpyHostToDevice, c->stream)) !=
-          hipSuccess ||
-      (!tab.empty() && (e = hipMemcpyAsync(c->d_pmc, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice,
-                                           c->stream)) != hipSuccess) ||
-      (e = hipMemsetAsync(c->d_scene, 0, B * np * 16 * sizeof(double), c->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-    return hfail("hipMemcpy", e);
   *out = c;
-  return THIP_OK;
-}
-
-static int ccsets_upload_scene(thip_ccsets* c, const double* scene, hipMemcpyKind kind, const char* who)
-{
-  if (!c)
-    return THIP_E_INVALID;
-  if (c->pr.n_prims > 0 && !scene)
-    return sfail(c, std::string(who) + ": scene required when n_prims > 0");
-  hipError_t e;
-  if ((e = hipSetDevice(c->device)) != hipSuccess)
-    return shipfail(c, "hipSetDevice", e);
-  if (c->pr.n_prims > 0 &&
-      ((e = hipMemcpyAsync(c->d_scene, scene,
-                           static_cast<size_t>(c->batch) * static_cast<size_t>(c->pr.n_prims) * 16 * sizeof(double), kind,
-                           c->stream)) != hipSuccess ||
-       (e = hipStreamSynchronize(c->stream)) != hipSuccess))
-    return shipfail(c, "hipMemcpy(scene)", e);
-  c->uploaded = true;
   return THIP_OK;
 }
 
 int thip_ccsets_upload(thip_ccsets* cs, const double* scene)
 {
-  return ccsets_upload_scene(cs, scene, hipMemcpyHostToDevice, "thip_ccsets_upload");
+  return upload_scene(cs, scene, hipMemcpyHostToDevice, "thip_ccsets_upload");
 }
 
 int thip_ccsets_upload_device(thip_ccsets* cs, const double* d_scene)
 {
-  return ccsets_upload_scene(cs, d_scene, hipMemcpyDeviceToDevice, "thip_ccsets_upload_device");
+  return upload_scene(cs, d_scene, hipMemcpyDeviceToDevice, "thip_ccsets_upload_device");
 }
 
 int thip_ccsets_segments(const thip_ccsets* cs) { return cs ? cs->pr.n_seg : THIP_E_INVALID; }
@@ -924,35 +697,16 @@ int thip_ccsets_segments(const thip_ccsets* cs) { return cs ? cs->pr.n_seg : THI
 int thip_ccsets_run(thip_ccsets* cs, const double* x, double* values, double* jac, double* coeffs, int* counts,
                     int* keys)
 {
-  if (!cs)
-    return THIP_E_INVALID;
-  if (!x)
-    return sfail(cs, "thip_ccsets_run: null x");
-  if (!cs->uploaded)
-    return sfail(cs, "thip_ccsets_run: thip_ccsets_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(cs->device)) != hipSuccess)
-    return shipfail(cs, "hipSetDevice", e);
-  if ((e = hipMemcpyAsync(cs->d_x, x,
-                          static_cast<size_t>(cs->batch) * static_cast<size_t>(cs->pr.N) * cs->D * sizeof(double),
-                          hipMemcpyHostToDevice, cs->stream)) != hipSuccess)
-    return shipfail(cs, "hipMemcpy(x)", e);
-  return run_on_device(cs, cs->d_x, values, jac, coeffs, counts, keys);
+  const double* d_x = nullptr;
+  const int rc = stage_x(cs, "thip_ccsets", x, true, d_x);
+  return rc != THIP_OK ? rc : run_on_device(cs, d_x, values, jac, coeffs, counts, keys);
 }
 
 int thip_ccsets_run_device(thip_ccsets* cs, const double* d_x, double* values, double* jac, double* coeffs,
                            int* counts, int* keys)
 {
-  if (!cs)
-    return THIP_E_INVALID;
-  if (!d_x)
-    return sfail(cs, "thip_ccsets_run_device: null d_x");
-  if (!cs->uploaded)
-    return sfail(cs, "thip_ccsets_run_device: thip_ccsets_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(cs->device)) != hipSuccess)
-    return shipfail(cs, "hipSetDevice", e);
-  return run_on_device(cs, d_x, values, jac, coeffs, counts, keys);
+  const int rc = stage_x(cs, "thip_ccsets", d_x, false, d_x);
+  return rc != THIP_OK ? rc : run_on_device(cs, d_x, values, jac, coeffs, counts, keys);
 }
 
 double thip_ccsets_last_ms(thip_ccsets* cs) { return cs ? cs->last_ms : -1.0; }
@@ -961,26 +715,8 @@ void thip_ccsets_destroy(thip_ccsets* cs)
 {
   if (!cs)
     return;
-  hipSetDevice(cs->device);
-  if (cs->stream)
-    hipStreamSynchronize(cs->stream);
-  hipFree(cs->d_chain);
-  hipFree(cs->d_model);
-  hipFree(cs->d_pmc);
+  release(cs);
   hipFree(cs->d_fixed);
-  hipFree(cs->d_scene);
-  hipFree(cs->d_x);
-  hipFree(cs->d_values);
-  hipFree(cs->d_jac);
-  hipFree(cs->d_coeffs);
-  hipFree(cs->d_counts);
-  hipFree(cs->d_keys);
-  if (cs->ev0)
-    hipEventDestroy(cs->ev0);
-  if (cs->ev1)
-    hipEventDestroy(cs->ev1);
-  if (cs->stream)
-    hipStreamDestroy(cs->stream);
   delete cs;
 }
 

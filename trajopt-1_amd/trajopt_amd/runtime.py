@@ -406,151 +406,126 @@ class TrajectoryChecker:
             pass
 
 
-class CollisionSets:
+class _CollisionSetsBase:
+    """What CollisionSets and ContinuousCollisionSets share.  A subclass sets _api (the
+    thip_<_api>_* symbols' prefix) and _count (the symbol that counts its nodes or
+    segments) and has _jac_shape(); its __init__ calls _create() with the arguments of
+    thip_<_api>_create between config and batch."""
+
+    _api = _count = ""
+    cs = None
+
+    def _fn(self, name):
+        return getattr(self.lib, f"thip_{self._api}_{name}")
+
+    def _create(self, desc, batch, scene, config, device, *extra):
+        """Creates the object, uploads the scene; returns the count of nodes or segments."""
+        self.lib = abi.load_hip()
+        self.batch = batch
+        self.n_steps, self.n_dof = desc.n_steps, desc.chain.n_dof
+        self.config = config
+        self.cs = C.c_void_p()
+        rc = self._fn("create")(device, C.byref(desc), C.byref(config), *extra, batch, C.byref(self.cs))
+        if rc != 0:
+            raise HipError(f"thip_{self._api}_create: {self._fn('last_error')(None).decode()}")
+        self._items = self._fn(self._count)(self.cs)
+        self.rows = config.max_num_cnt
+        self._scene = np.ascontiguousarray(scene, dtype=np.float64) if desc.n_prims > 0 else None
+        if self._scene is not None and self._scene.size != batch * desc.n_prims * 16:
+            self.close()
+            raise HipError(f"{type(self).__name__}: scene has {self._scene.size} values, not [batch][n_prims][16]")
+        self._check(self._fn("upload")(self.cs, None if self._scene is None else _dp(self._scene)),
+                    f"thip_{self._api}_upload")
+        return self._items
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise HipError(f"{what}: {self._fn('last_error')(self.cs).decode()}")
+
+    def _out(self):
+        rows = (self.batch, self._items, self.rows)
+        return (np.zeros(rows), np.zeros(rows + self._jac_shape()), np.zeros(rows),
+                np.zeros(rows[:2], dtype=np.int32), np.zeros(rows + (4,), dtype=np.int32))
+
+    @staticmethod
+    def _ip(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int))
+
+    def _run(self, name, x):
+        v, J, cf, cnt, keys = self._out()
+        self._check(self._fn(name)(self.cs, x, _dp(v), _dp(J), _dp(cf), self._ip(cnt), self._ip(keys)),
+                    f"thip_{self._api}_{name}")
+        return v, J, cf, cnt, keys
+
+    def run(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != self.batch * self.n_steps * self.n_dof:
+            raise HipError(f"{type(self).__name__}.run: x has {x.size} values, not [batch][n_steps][n_dof]")
+        return self._run("run", _dp(x))
+
+    def run_device(self, d_x):
+        """As run() on trajectories already on the device (an address)."""
+        return self._run("run_device", C.c_void_p(d_x))
+
+    def kernel_ms(self) -> float:
+        return float(self._fn("last_ms")(self.cs))
+
+    def close(self):
+        if self.cs:
+            self._fn("destroy")(self.cs)
+            self.cs = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CollisionSets(_CollisionSetsBase):
     """thip_csets_*: the rows of trajopt_ifopt's fixed-size DiscreteCollisionConstraint
     (SingleTimestepCollisionEvaluator) at every node of [first_step, last_step]
     of every problem, one launch per x.  Reads the chain, robot spheres,
     self-collision pairs, n_prims, n_steps and collision term 0's coll_pairs of
     `desc`; config: abi.CsetsConfig; scene [B, n_prims, 16]."""
 
+    _api, _count = "csets", "nodes"
+
     def __init__(self, desc, batch, scene, config, device: int = 0):
-        self.lib = abi.load_hip()
-        self.batch = batch
-        self.n_steps, self.n_dof = desc.n_steps, desc.chain.n_dof
-        self.config = config
-        self.cs = C.c_void_p()
-        rc = self.lib.thip_csets_create(device, C.byref(desc), C.byref(config), batch, C.byref(self.cs))
-        if rc != 0:
-            raise HipError(f"thip_csets_create: {self.lib.thip_csets_last_error(None).decode()}")
-        self.n_nodes = self.lib.thip_csets_nodes(self.cs)
-        self.rows = config.max_num_cnt
-        self._scene = np.ascontiguousarray(scene, dtype=np.float64) if desc.n_prims > 0 else None
-        if self._scene is not None and self._scene.size != batch * desc.n_prims * 16:
-            self.close()
-            raise HipError(f"CollisionSets: scene has {self._scene.size} values, not [batch][n_prims][16]")
-        self._check(self.lib.thip_csets_upload(self.cs, None if self._scene is None else _dp(self._scene)),
-                    "thip_csets_upload")
+        self.n_nodes = self._create(desc, batch, scene, config, device)
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise HipError(f"{what}: {self.lib.thip_csets_last_error(self.cs).decode()}")
-
-    def _out(self):
-        B, n, R = self.batch, self.n_nodes, self.rows
-        return (np.zeros((B, n, R)), np.zeros((B, n, R, self.n_dof)), np.zeros((B, n, R)),
-                np.zeros((B, n), dtype=np.int32), np.zeros((B, n, R, 4), dtype=np.int32))
-
-    @staticmethod
-    def _ip(a):
-        return a.ctypes.data_as(C.POINTER(C.c_int))
+    def _jac_shape(self):
+        return (self.n_dof,)
 
     def run(self, x):
         """x [B, N, D] (host) -> values [B, n, R], jac [B, n, R, D], coeffs [B, n, R],
         counts [B, n], keys [B, n, R, 4] (link, other, sphere, other_sphere)."""
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        if x.size != self.batch * self.n_steps * self.n_dof:
-            raise HipError(f"CollisionSets.run: x has {x.size} values, not [batch][n_steps][n_dof]")
-        v, J, cf, cnt, keys = self._out()
-        self._check(self.lib.thip_csets_run(self.cs, _dp(x), _dp(v), _dp(J), _dp(cf), self._ip(cnt), self._ip(keys)),
-                    "thip_csets_run")
-        return v, J, cf, cnt, keys
-
-    def run_device(self, d_x):
-        """As run() on trajectories already on the device (an address)."""
-        v, J, cf, cnt, keys = self._out()
-        self._check(self.lib.thip_csets_run_device(self.cs, C.c_void_p(d_x), _dp(v), _dp(J), _dp(cf), self._ip(cnt),
-                                                   self._ip(keys)), "thip_csets_run_device")
-        return v, J, cf, cnt, keys
-
-    def kernel_ms(self) -> float:
-        return float(self.lib.thip_csets_last_ms(self.cs))
-
-    def close(self):
-        if self.cs:
-            self.lib.thip_csets_destroy(self.cs)
-            self.cs = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().run(x)
 
 
-class ContinuousCollisionSets:
+class ContinuousCollisionSets(_CollisionSetsBase):
     """thip_ccsets_*: the rows of trajopt_ifopt's fixed-size ContinuousCollisionConstraint
     (LVSContinuousCollisionEvaluator / LVSDiscreteCollisionEvaluator) on every segment
     (t, t + 1), first_step <= t < last_step, of every problem, one launch per x.  Reads
     what CollisionSets reads of `desc`; config: abi.CcsetsConfig; scene [B, n_prims, 16];
     seg_fixed: per segment bit 0 = vars0 fixed, bit 1 = vars1 fixed (None: no end fixed)."""
 
+    _api, _count = "ccsets", "segments"
+
     def __init__(self, desc, batch, scene, config, seg_fixed=None, device: int = 0):
-        self.lib = abi.load_hip()
-        self.batch = batch
-        self.n_steps, self.n_dof = desc.n_steps, desc.chain.n_dof
-        self.config = config
-        self.cs = C.c_void_p()
         fixed = None
         if seg_fixed is not None:
             fixed = np.ascontiguousarray(seg_fixed, dtype=np.int32)
             n = config.last_step - config.first_step
             if fixed.size != max(n, 0) and n > 0:
                 raise HipError(f"ContinuousCollisionSets: seg_fixed has {fixed.size} entries, not {n}")
-        rc = self.lib.thip_ccsets_create(device, C.byref(desc), C.byref(config),
-                                         None if fixed is None else self._ip(fixed), batch, C.byref(self.cs))
-        if rc != 0:
-            raise HipError(f"thip_ccsets_create: {self.lib.thip_ccsets_last_error(None).decode()}")
-        self.n_segments = self.lib.thip_ccsets_segments(self.cs)
-        self.rows = config.max_num_cnt
-        self._scene = np.ascontiguousarray(scene, dtype=np.float64) if desc.n_prims > 0 else None
-        if self._scene is not None and self._scene.size != batch * desc.n_prims * 16:
-            self.close()
-            raise HipError(f"ContinuousCollisionSets: scene has {self._scene.size} values, not [batch][n_prims][16]")
-        self._check(self.lib.thip_ccsets_upload(self.cs, None if self._scene is None else _dp(self._scene)),
-                    "thip_ccsets_upload")
+        self.n_segments = self._create(desc, batch, scene, config, device, None if fixed is None else self._ip(fixed))
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise HipError(f"{what}: {self.lib.thip_ccsets_last_error(self.cs).decode()}")
-
-    def _out(self):
-        B, n, R = self.batch, self.n_segments, self.rows
-        return (np.zeros((B, n, R)), np.zeros((B, n, R, 2, self.n_dof)), np.zeros((B, n, R)),
-                np.zeros((B, n), dtype=np.int32), np.zeros((B, n, R, 4), dtype=np.int32))
-
-    @staticmethod
-    def _ip(a):
-        return a.ctypes.data_as(C.POINTER(C.c_int))
+    def _jac_shape(self):
+        return (2, self.n_dof)
 
     def run(self, x):
         """x [B, N, D] (host) -> values [B, n, R], jac [B, n, R, 2, D] (end 0 = node t, end 1 =
         node t + 1), coeffs [B, n, R], counts [B, n], keys [B, n, R, 4].  Raises when a segment
         needs more than abi.CCSETS_MAX_SUBSTATES states."""
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        if x.size != self.batch * self.n_steps * self.n_dof:
-            raise HipError(f"ContinuousCollisionSets.run: x has {x.size} values, not [batch][n_steps][n_dof]")
-        v, J, cf, cnt, keys = self._out()
-        self._check(self.lib.thip_ccsets_run(self.cs, _dp(x), _dp(v), _dp(J), _dp(cf), self._ip(cnt), self._ip(keys)),
-                    "thip_ccsets_run")
-        return v, J, cf, cnt, keys
-
-    def run_device(self, d_x):
-        """As run() on trajectories already on the device (an address)."""
-        v, J, cf, cnt, keys = self._out()
-        self._check(self.lib.thip_ccsets_run_device(self.cs, C.c_void_p(d_x), _dp(v), _dp(J), _dp(cf), self._ip(cnt),
-                                                    self._ip(keys)), "thip_ccsets_run_device")
-        return v, J, cf, cnt, keys
-
-    def kernel_ms(self) -> float:
-        return float(self.lib.thip_ccsets_last_ms(self.cs))
-
-    def close(self):
-        if self.cs:
-            self.lib.thip_ccsets_destroy(self.cs)
-            self.cs = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().run(x)
