@@ -332,7 +332,9 @@ typedef struct thip_problem_desc {
    * other cost term but collision, constraints every other constraint but
    * collision.  The fused sqp_kernel lowers JointAccEqCost (order 2, cost, zero
    * tolerances) when thip_jdt_fused() holds: the reduced KKT matrix is then
-   * block-tridiagonal over waypoint PAIRS (2 D-wide blocks).  Every other form is
+   * block-tridiagonal over waypoint PAIRS (2 D-wide blocks); its steps must be the
+   * clamped ones, 0 <= jdt_first_step and jdt_first_step + 2 <= jdt_last_step <=
+   * n_steps - 1 (thip_create and thip_terms_create refuse others).  Every other form is
    * refused by thip_create and runs the generic path (sco::BasicTrustRegionSQP
    * on the host with the GpuModel); this table is also the record the oracle
    * reads. */

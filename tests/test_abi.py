@@ -73,6 +73,15 @@ def _with_collision(d, evaluator):
     d.coll_continuous = evaluator
 
 
+def _with_joint_acc(d, first, last):
+    """A JointAccEqCost (order 2, cost, zero tolerances: thip_jdt_fused holds) on steps first..last as given."""
+    d.n_jdt = 1
+    d.jdt_order[0] = 2
+    d.jdt_first_step[0], d.jdt_last_step[0] = first, last
+    for j in range(d.chain.n_dof):
+        d.jdt_coeffs[0][j] = 1.0
+
+
 def _create(lib, desc, batch=4):
     ctx = C.c_void_p()
     rc = lib.thip_create(0, C.byref(desc), batch, C.byref(ctx))
@@ -95,6 +104,10 @@ def _create(lib, desc, batch=4):
         (lambda d: setattr(d, "n_jvx", 5), "n_jvx"),
         (lambda d: setattr(d, "n_jvx", 1), "tolerance forms"),
         (lambda d: _with_collision(d, 3), "coll_continuous"),
+        # a JointAccEqCost's steps index x as given (config A: 10 waypoints)
+        (lambda d: _with_joint_acc(d, 0, 10), "jdt_last_step"),   # last = n_steps
+        (lambda d: _with_joint_acc(d, -1, 9), "jdt_first_step"),  # first = -1
+        (lambda d: _with_joint_acc(d, 4, 5), "jdt_first_step + 2 <= jdt_last_step"),  # last = first + 1
     ],
 )
 def test_create_rejects_invalid_descriptors(lib, mutate, needle):
@@ -106,6 +119,18 @@ def test_create_rejects_invalid_descriptors(lib, mutate, needle):
     assert not ctx
     msg = lib.thip_last_error(None).decode()
     assert needle.lower() in msg.lower(), msg
+
+
+def test_create_rejects_joint_acc_on_two_waypoints(lib):
+    """with_joint_acc clamps like JointAccTermInfo::hatch, which on 2 waypoints gives
+    first_step = N - 3 = -1: refused with the range's message, not run."""
+    wl = problems.with_joint_acc(problems.make_workload("B", 1, n_steps=2))
+    assert (wl.desc.jdt_first_step[0], wl.desc.jdt_last_step[0]) == (-1, 1)
+    assert lib.thip_jdt_fused(C.byref(wl.desc)) == 1  # the form is the fused one; only its range is not
+    rc, ctx = _create(lib, wl.desc)
+    assert rc == -1 and not ctx
+    msg = lib.thip_last_error(None).decode()
+    assert "jdt_first_step" in msg and "jdt_last_step" in msg and "(got -1, 1 on 2 waypoints)" in msg, msg
 
 
 def test_create_rejects_bad_batch(lib):

@@ -44,7 +44,8 @@ def solve_gpu(wl, trace=0):
 
 
 # ------------------------------------------------------------------ kinematics
-@pytest.mark.parametrize("robot", ["right_arm", "torso_right_arm", "right_arm_6dof"])
+@pytest.mark.parametrize("robot", ["right_arm", "torso_right_arm", "right_arm_6dof", "right_arm_1dof",
+                                   "right_arm_3dof"])
 def test_fwd_kin_parity(oracle_mod, robot):
     wl = problems.make_workload("B", 4, robot=robot)
     s = BatchTrustRegionSQP(wl)
@@ -92,6 +93,22 @@ def test_cartpose_linearization_parity(oracle_mod, cfg, B):
     np.testing.assert_allclose(err, eo, rtol=0, atol=1e-12)
     # forward differences with eps = 1e-5 (kinematic_terms.hpp:15) amplify
     # last-bit FK differences by 1e5
+    np.testing.assert_allclose(jac, jo, rtol=0, atol=1e-9)
+
+
+@pytest.mark.parametrize("robot", ["right_arm_1dof", "right_arm_3dof"])
+def test_cartpose_linearization_parity_small_chains(oracle_mod, robot):
+    """test_cartpose_linearization_parity's check on config B over chains of 1 and 3 dofs
+    (robots.ROBOTS: the later joints held fixed): Jacobians of 1 and 3 columns."""
+    wl = problems.make_workload("B", 8, robot=robot)
+    rng = np.random.default_rng(7)
+    x = wl.init + rng.normal(0, 0.05, wl.init.shape)
+    s = BatchTrustRegionSQP(wl)
+    err, jac = s.linearize(x)
+    s.close()
+    eo, jo = oracle_mod.linearize(wl, x)
+    assert jac.shape[-1] == wl.n_dof == int(robot[-4]) and np.abs(jo).max() > 0.1
+    np.testing.assert_allclose(err, eo, rtol=0, atol=1e-12)
     np.testing.assert_allclose(jac, jo, rtol=0, atol=1e-9)
 
 
@@ -289,6 +306,25 @@ def test_collision_rows_parity(oracle_mod):
     for b in range(wl.batch):
         _check_rows(rows[b], oracle_mod.collision_rows(wl, b, xo[b]), f"problem {b} (solution)")
         _check_rows(rows_init[b], oracle_mod.collision_rows(wl, b, wl.init[b]), f"problem {b} (init)")
+
+
+@pytest.mark.parametrize("robot", ["right_arm_1dof", "right_arm_3dof"])
+def test_collision_rows_parity_small_chains(oracle_mod, robot):
+    """Config C's contact rows over chains of 1 and 3 dofs (robots.ROBOTS: the later joints
+    held fixed, so the spheres of the held links still collide but their gradient rows have
+    1 or 3 columns per waypoint), at the initial and at a perturbed trajectory.  A contact
+    distance of 0.325 m (coll_buffer 0.3) gives every problem thousands of rows."""
+    wl = problems.make_workload("C", 4, robot=robot)
+    wl.desc.coll_buffer = 0.3
+    x = wl.init + np.random.default_rng(7).normal(0, 0.05, wl.init.shape)
+    s = BatchTrustRegionSQP(wl)
+    rows_init = s.collision_rows(wl.init, cap=8192)
+    rows = s.collision_rows(x, cap=8192)
+    s.close()
+    assert min(len(r) for r in rows_init) > 1000 and rows[0].shape[1] == 8 + 2 * int(robot[-4]) + 1
+    for b in range(wl.batch):
+        _check_rows(rows_init[b], oracle_mod.collision_rows(wl, b, wl.init[b]), f"problem {b} (init)")
+        _check_rows(rows[b], oracle_mod.collision_rows(wl, b, x[b]), f"problem {b} (perturbed)")
 
 
 def _continuous(wl):

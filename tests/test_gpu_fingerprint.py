@@ -29,7 +29,13 @@ at batch 8, on the 8-dof torso_right_arm, at 3 waypoints on problems 4..7 (one
 without a hinge row; the pointer prefix ends among the aux or hinge columns),
 problem 833 alone (hundreds of hinge rows in a step pair), and at 50 waypoints,
 which runs the generic-step build (sqp_kernel_gen; 350 x columns on 256
-threads: two column chunks).
+threads: two column chunks).  Chains narrower than the lane octet
+(robots.ROBOTS' right_arm_<k>dof): config B on 2 dofs at 3 waypoints and on 3
+dofs, config C on 5 dofs.  The 1-dof chain is left to the other two-path
+modules: its single Jacobian column never changes pattern (no cold QP after the
+first in any of problems 0..4095 of config B at 3 waypoints, by the oracle's QP
+trace), so "both answers occur" cannot hold on it; 2 dofs is the narrowest chain
+on which it does.
 """
 import ctypes as C
 
@@ -51,6 +57,9 @@ CASES = {
     "C-n3": ("C", 4, dict(n_steps=3, first_problem=4), False, True),
     "C-833": ("C", 1, dict(first_problem=833), False, False),
     "C-n50": ("C", 4, dict(n_steps=50), True, True),
+    "B-d2-n3": ("B", 4, dict(n_steps=3, robot="right_arm_2dof"), False, True),
+    "B-d3": ("B", 4, dict(robot="right_arm_3dof"), False, True),
+    "C-d5": ("C", 8, dict(robot="right_arm_5dof"), False, True),
 }
 
 

@@ -29,7 +29,11 @@ first block of a half without a coupling); config A (a CartPose constraint, 10
 waypoints); config C (hinge rows) at batch 8, on the 8-dof torso_right_arm
 (the full octet: no identity padding), and problem 833 alone, whose hundreds of hinge rows in one pair leave A_HC in HBM
 (also checked against the oracle); and config C at 50 waypoints, which runs the
-generic-step build of the kernel (sqp_kernel_gen).
+generic-step build of the kernel (sqp_kernel_gen).  Chains narrower than the
+lane octet (robots.ROBOTS' right_arm_<k>dof: chol_inv_block_reg pads inside the
+octet): config B on 1 dof at 3 waypoints and on 3 dofs, config C on 5 dofs, and
+config B on 2 dofs with a JointAccEqCost -- waypoint-pair blocks of 4 dofs on the
+generic-step build (the in-register Cholesky at sD = 4 with dense couplings).
 """
 import ctypes as C
 
@@ -54,6 +58,10 @@ CASES = {
     "C-torso": ("C", 4, dict(robot="torso_right_arm", first_problem=0), True, False),
     "C-833": ("C", 1, dict(first_problem=833), True, False),
     "C-n50": ("C", 4, dict(n_steps=50, first_problem=0), True, True),
+    "B-d1-n3": ("B", 4, dict(n_steps=3, robot="right_arm_1dof", first_problem=0), False, False),
+    "B-d3": ("B", 4, dict(robot="right_arm_3dof", first_problem=0), False, False),
+    "C-d5": ("C", 8, dict(robot="right_arm_5dof", first_problem=0), True, False),
+    "B-acc-d2": ("B+acc", 4, dict(robot="right_arm_2dof", first_problem=0), False, True),
 }
 ORACLE_CASES = ("C-833",)
 
@@ -65,6 +73,13 @@ def hip():
 
     assert torch.cuda.is_available(), "gpu tests need an AMD GPU"
     return lib
+
+
+def make(cfg, batch, kw):
+    """CASES' workload; '<config>+acc' adds a JointAccEqCost (waypoint-pair blocks)."""
+    if cfg.endswith("+acc"):
+        return problems.with_joint_acc(problems.make_workload(cfg[:-4], batch, **kw))
+    return problems.make_workload(cfg, batch, **kw)
 
 
 def solve(wl, path):
@@ -116,7 +131,7 @@ def runs():
     def get(name):
         if name not in cache:
             cfg, batch, kw, _, _ = CASES[name]
-            wl = problems.make_workload(cfg, batch, **kw)
+            wl = make(cfg, batch, kw)
             cache[name] = (wl, solve(wl, 0), solve(wl, abi.DEBUG_SETUP_REF))
         return cache[name]
 

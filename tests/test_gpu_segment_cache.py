@@ -30,6 +30,9 @@ batch 8 and on
 the 8-dof torso_right_arm (the full lane octet); and config C's problems 435 and
 833 alone, whose ~436 and ~758 mean hinge rows put the hinge pack in HBM with
 A_HCT in LDS, and both in HBM.  Those two are also checked against the oracle.
+Chains narrower than the lane octet (robots.ROBOTS' right_arm_<k>dof: blocks
+padded with identity from 1, 3 and 5 dofs up to 8 lanes): config B on 1 dof at 3
+waypoints and on 3 dofs, config C on 5 dofs.
 """
 import ctypes as C
 
@@ -53,6 +56,11 @@ CASES = {
     "C-torso": ("C", 4, dict(robot="torso_right_arm", first_problem=0)),
     "C-435": ("C", 1, dict(first_problem=435)),
     "C-833": ("C", 1, dict(first_problem=833)),
+    # chains narrower than the lane octet; windows with a rejected step (problems 102 and 43:
+    # none of problems 0..95 on 1 dof and 0..31 on 3 dofs solves a second QP on one convexification)
+    "B-d1-n3": ("B", 4, dict(n_steps=3, robot="right_arm_1dof", first_problem=100)),
+    "B-d3": ("B", 4, dict(robot="right_arm_3dof", first_problem=40)),
+    "C-d5": ("C", 8, dict(robot="right_arm_5dof", first_problem=0)),
 }
 ORACLE_CASES = ("C-435", "C-833")
 

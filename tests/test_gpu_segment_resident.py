@@ -30,7 +30,9 @@ against the oracle; and an infeasible config B (the fixed first waypoint 0.3
 above joint 3's upper limit) at both lengths: every QP ends primal infeasible
 (trace status 3) after a few hundred iterations and the run ends with status 4
 -- the path on which all three precomputed tests pass and the full function
-alone decides.
+alone decides.  Chains narrower than the lane octet (robots.ROBOTS'
+right_arm_<k>dof): config B on 1 dof at 3 waypoints and on 3 dofs, config C on
+5 dofs.
 """
 import ctypes as C
 
@@ -58,6 +60,10 @@ CASES = {
     "C-833": ("C", 1, dict(first_problem=833), False),
     "B-n3-infeasible": ("B", 2, dict(n_steps=3, first_problem=0), True),
     "B-n32-infeasible": ("B", 2, dict(n_steps=32, first_problem=0), True),
+    # chains narrower than the lane octet (pads of 7, 5 and 3 lanes)
+    "B-d1-n3": ("B", 4, dict(n_steps=3, robot="right_arm_1dof", first_problem=0), False),
+    "B-d3": ("B", 4, dict(robot="right_arm_3dof", first_problem=0), False),
+    "C-d5": ("C", 8, dict(robot="right_arm_5dof", first_problem=0), False),
 }
 ORACLE_CASES = ("C-833",)
 

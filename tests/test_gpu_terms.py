@@ -96,6 +96,9 @@ VARIANTS = {
     "jpos_ineq": lambda: problems.make_reference_unit("joint_pos_ineq", 3),
     "jvel_ineq": lambda: problems.make_reference_unit("joint_vel_ineq", 3),
     "jacc6": lambda: problems.make_workload("HA", 3, n_steps=6),
+    # a JointAccEqCost on 2 dofs: the solver runs narrow waypoint-pair blocks (2 and 3 of them)
+    "jacc4_2dof": lambda: problems.make_workload("HA", 3, n_steps=4, robot="right_arm_2dof"),
+    "jacc6_2dof": lambda: problems.make_workload("HA", 3, n_steps=6, robot="right_arm_2dof"),
     "pairs6": lambda: coll_workload(0, False, pairs=True),
     "fixed_end_cast7": lambda: coll_workload(1, False, n_steps=7, fixed_end=True),
     "C30": lambda: coll_workload(1, False, n_steps=30),

@@ -27,12 +27,15 @@ def test_fk_oracle_vs_numpy(oracle_mod, golden):
     np.testing.assert_allclose(poses, g["poses_numpy"], rtol=0, atol=1e-12)
 
 
-@pytest.mark.parametrize("robot", ["torso_right_arm", "right_arm_6dof"])
+@pytest.mark.parametrize("robot", ["torso_right_arm", "right_arm_6dof", "right_arm_1dof", "right_arm_3dof"])
 def test_fk_oracle_vs_numpy_other_chains(oracle_mod, robot):
-    """The prismatic torso_lift_joint (8 DoF) and a 6-DoF chain: oracle FK
-    against the numpy FK, and the torso joint moves the arm along +z."""
+    """The prismatic torso_lift_joint (8 DoF), a 6-DoF chain and the 1- and 3-DoF
+    chains (the later joints held fixed): oracle FK against the numpy FK, and the
+    torso joint moves the arm along +z."""
     wl = problems.make_workload("A", 4, robot=robot)
     chain = wl.desc.chain
+    if robot.endswith("dof"):
+        assert chain.n_dof == int(robot[-4]) and chain.n_links == robots.pr2_right_arm().n_links
     q = wl.init.reshape(-1, wl.n_dof)
     poses = oracle_mod.fwd_kin(chain, q)
     for i in range(q.shape[0]):
@@ -44,6 +47,22 @@ def test_fk_oracle_vs_numpy_other_chains(oracle_mod, robot):
         q2[:, 0] += 0.1
         d = oracle_mod.fwd_kin(chain, q2)[:, -1, [3, 7, 11]] - poses[:, -1, [3, 7, 11]]
         np.testing.assert_allclose(d, np.tile([0.0, 0.0, 0.1], (q.shape[0], 1)), atol=1e-12)
+
+
+@pytest.mark.parametrize("k", range(1, 7))
+def test_small_chains_are_the_right_arm_with_later_joints_at_zero(oracle_mod, k):
+    """robots.ROBOTS' right_arm_<k>dof: the same links, tool link and link offset as
+    right_arm, and every link's pose that of right_arm with joints k.. at 0."""
+    build, tool, offset = robots.ROBOTS[f"right_arm_{k}dof"]
+    assert (tool, offset) == robots.ROBOTS["right_arm"][1:]
+    chain, full = build(), robots.pr2_right_arm()
+    assert chain.n_dof == k and chain.n_links == full.n_links
+    lo, hi, _ = robots.chain_limits(full)
+    np.testing.assert_array_equal(np.stack(robots.chain_limits(chain)[:2]), np.stack([lo[:k], hi[:k]]))
+    rng = np.random.default_rng(k)
+    q = np.zeros((5, 7))
+    q[:, :k] = rng.uniform(-1.0, 1.0, (5, k))
+    np.testing.assert_allclose(oracle_mod.fwd_kin(chain, q[:, :k]), oracle_mod.fwd_kin(full, q), rtol=0, atol=1e-15)
 
 
 def test_fk_oracle_vs_numpy_dual_arm_tree(oracle_mod):

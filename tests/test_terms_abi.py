@@ -61,9 +61,22 @@ def _non_fused_jdt(d):
     d.jdt_first_step[0], d.jdt_last_step[0] = 0, 6
 
 
+def _joint_acc(first, last):
+    # a JointAccEqCost of the fused form (6 waypoints, 7 dofs) on steps first..last as given
+    def mutate(d):
+        d.n_jdt = 1
+        d.jdt_order[0] = 2
+        d.jdt_first_step[0], d.jdt_last_step[0] = first, last
+
+    return mutate
+
+
 @pytest.mark.parametrize(
     "config, mutate, needle, host_loop",
     [
+        ("A", _joint_acc(0, 6), "jdt_last_step", False),    # last = n_steps
+        ("A", _joint_acc(-1, 5), "jdt_first_step", False),  # first = -1
+        ("A", _joint_acc(2, 3), "jdt_first_step + 2 <= jdt_last_step", False),  # last = first + 1
         ("A", lambda d: setattr(d, "abi_version", abi.ABI_VERSION + 1), "abi_version", False),
         ("C", _coll_extra, "coll_extra", True),
         ("A", lambda d: setattr(d, "use_time", 1), "use_time", True),

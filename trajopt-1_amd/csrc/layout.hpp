@@ -251,7 +251,9 @@ struct Layout
   // matrix is block-tridiagonal over pairs, not over waypoints): grp = 2 makes
   // solve block T waypoints 2T and 2T + 1 (sD = 2 D, sN = N / 2; the solve
   // layout is the column order itself).  grp = 1 otherwise.  sNb: solve blocks
-  // per branch (N / grp), the length of each twisted factorisation.
+  // per branch (N / grp), the length of each twisted factorisation.  Pairs run
+  // the generic step at every width: narrow (D <= 4, sD <= 8) or wide, never
+  // the ADMM segment, whose chain pack is one waypoint per block (seg_ok = 0).
   int grp;
   int sNb;
   // the CartPose rows of every waypoint are contiguous and in order (step_rows

@@ -559,6 +559,12 @@ std::string validate_terms(const thip_problem_desc* d)
   }
   if (!thip_jdt_fused(d))
     return std::string("JointAcc / JointJerk terms other than the fused JointAccEqCost (non-fused jdt)") + kHostLoop;
+  for (int k = 0; k < d->n_jdt; ++k)
+    if (d->jdt_first_step[k] < 0 || d->jdt_first_step[k] + 2 > d->jdt_last_step[k] ||
+        d->jdt_last_step[k] > d->n_steps - 1)
+      return "jdt term " + std::to_string(k) + ": need 0 <= jdt_first_step and jdt_first_step + 2 <= "
+             "jdt_last_step <= n_steps - 1 (got " + std::to_string(d->jdt_first_step[k]) + ", " +
+             std::to_string(d->jdt_last_step[k]) + " on " + std::to_string(d->n_steps) + " waypoints)";
   if (d->use_time != 0 || d->n_jvt != 0 || d->n_ttt != 0 || d->n_fixed_dofs != 0)
     return std::string("time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs") +
            kHostLoop;

@@ -239,6 +239,15 @@ static int validate(const thip_problem_desc* d, std::string& why)
                  "2 n_dof <= THIP_MAX_DOF, and JointVel equality constraints, are not lowered into the batched "
                  "kernel: solve such a problem with sco::BasicTrustRegionSQP (the generic path, GpuModel)",
            THIP_E_INVALID;
+  // the kernels index x with a JointAccEqCost term's steps as given (jacc_value,
+  // build_and_scale, term_values.hip): the range JointAccTermInfo::hatch clamps to
+  for (int k = 0; k < d->n_jdt; ++k)
+    if (d->jdt_first_step[k] < 0 || d->jdt_first_step[k] + 2 > d->jdt_last_step[k] ||
+        d->jdt_last_step[k] > d->n_steps - 1)
+      return why = "jdt term " + std::to_string(k) + ": need 0 <= jdt_first_step and jdt_first_step + 2 <= "
+                   "jdt_last_step <= n_steps - 1 (got " + std::to_string(d->jdt_first_step[k]) + ", " +
+                   std::to_string(d->jdt_last_step[k]) + " on " + std::to_string(d->n_steps) + " waypoints)",
+             THIP_E_INVALID;
   if (d->use_time != 0 || d->n_jvt != 0 || d->n_ttt != 0 || d->n_fixed_dofs != 0)
     return why = "time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs are not "
                  "lowered into the batched kernel: solve such a problem with sco::BasicTrustRegionSQP (the generic "
@@ -749,8 +758,9 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
   L.part_w = (2 * L.D <= 16) ? 16 : 32;
   sizes[A_HPART] = L.hinge ? nchk_cap * L.part_w : 1;
   sizes[A_HCT] = L.hinge ? 2 * D * (hc + 1) : 1;
-  // the segment's chain pack: narrow blocks and N <= 32 only (the segment's domain)
-  const bool cpk = !L.wide && L.N * 8 <= kBlock && L.N <= 2 * kCpkSteps;
+  // the segment's chain pack: narrow blocks, one waypoint per block and N <= 32 only (the
+  // segment's domain; seg_chain_pack reads D x D blocks over N waypoints, not pair blocks)
+  const bool cpk = !L.wide && L.grp == 1 && L.N * 8 <= kBlock && L.N <= 2 * kCpkSteps;
   sizes[A_CPK] = cpk ? kCpk : 1;
   for (int k = 0; k < A_COUNT; ++k)
     if (sizes[k] < 0)
@@ -807,8 +817,13 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     // QPs outside the register-resident segment's domain (below) run the
     // generic ADMM step for the whole solve: the generic-step build of the fused
     // kernel (kGenBlock threads, no segment code) takes them; its larger static
-    // LDS (reductions over 16 waves) leaves a smaller dynamic budget
-    const bool seg_cand = max_step_rows <= kMaxStepRows && !L.wide && L.N * 8 <= kBlock && L.n_abs <= kBlock && cpk;
+    // LDS (reductions over 16 waves) leaves a smaller dynamic budget.  Waypoint
+    // pairs (grp == 2) are outside it at every width: the segment's chain, its
+    // tw_mid and its P x know one waypoint per block and no (t, t + 2) coupling,
+    // so a JointAccEqCost problem on 4 or fewer dofs (sD = 2 D <= 8, narrow) runs
+    // the generic step like the wide ones
+    const bool seg_cand = max_step_rows <= kMaxStepRows && !L.wide && L.grp == 1 && L.N * 8 <= kBlock &&
+                          L.n_abs <= kBlock && cpk;
     // (contact_test_type FIRST / CLOSEST: only the generic-step build's contact scan selects among a call's contacts)
     const bool ctest = d.coll_enabled && d.coll_contact_test != THIP_CONTACT_ALL;
     ctx->gen = ctest || (!seg_cand && !(g_debug_path & THIP_DEBUG_MAIN_BUILD)) ||

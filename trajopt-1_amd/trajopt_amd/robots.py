@@ -19,6 +19,7 @@ named "both_arms" here.
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import numpy as np
@@ -88,10 +89,21 @@ def pr2_both_arms() -> Chain:
                   parents=[0] + list(range(1, 11)) + [0] + list(range(12, 22)))
 
 
-def pr2_right_arm_6dof() -> Chain:
-    joints = [(n, JOINT_FIXED, xyz, None, None) if n == "r_wrist_roll_joint" else (n, t, xyz, ax, lim)
+def pr2_right_arm_first(k: int) -> Chain:
+    """The right arm with its first k moving joints (1 <= k <= 7) and the last 7 - k held fixed at 0
+    (a fixed joint at the same origin): every link, the tool link and the sphere links keep their
+    indices, so the collision model, the scenes and the CartPose targets of right_arm apply as they are."""
+    moving = [n for n, t, _, _, _ in PR2_RIGHT_ARM if t != JOINT_FIXED]
+    if not 1 <= k <= len(moving):
+        raise ValueError(f"right arm: {k} moving joints")
+    held = set(moving[k:])
+    joints = [(n, JOINT_FIXED, xyz, None, None) if n in held else (n, t, xyz, ax, lim)
               for n, t, xyz, ax, lim in PR2_RIGHT_ARM]
     return _chain(PR2_TORSO_WORLD, joints)
+
+
+def pr2_right_arm_6dof() -> Chain:
+    return pr2_right_arm_first(6)  # r_wrist_roll_joint held
 
 
 ROBOTS = {
@@ -100,6 +112,11 @@ ROBOTS = {
     "right_arm_6dof": (pr2_right_arm_6dof, PR2_TOOL_LINK, 0),
     "both_arms": (pr2_both_arms, 22, 0),  # config E; its CartPose terms use both tool links
 }
+# right_arm_1dof ... right_arm_5dof: chains narrower than the solve's lane octet (the padded widths of
+# the fused kernel's narrow blocks; with a JointAccEqCost, waypoint-pair blocks of 2, 4, 6 and 8 dofs)
+for _k in range(1, 6):
+    ROBOTS[f"right_arm_{_k}dof"] = (functools.partial(pr2_right_arm_first, _k), PR2_TOOL_LINK, 0)
+del _k
 # both_arms (config E): tool links of the two arms
 PR2_BOTH_TOOL_LINKS = (11, 22)
 
