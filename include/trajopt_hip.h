@@ -260,7 +260,7 @@ typedef struct thip_problem_desc {
    * trajectory_costs.cpp:303-374).  A tolerance counts as zero when
    * |tol| < 1e-5 (trajopt_common::doubleEquals). */
   int jv_enabled;
-  int jv_first_step;
+  int jv_first_step;       /* >= 0 (hatch clamps it from above only): thip_create and thip_terms_create refuse less */
   int jv_last_step;
   double jv_coeffs[THIP_MAX_DOF];
   double jv_targets[THIP_MAX_DOF];
@@ -318,7 +318,7 @@ typedef struct thip_problem_desc {
    * constraint terms. */
   int n_jvx;
   int jvx_is_cnt[THIP_MAX_JVX];
-  int jvx_first_step[THIP_MAX_JVX];
+  int jvx_first_step[THIP_MAX_JVX];  /* >= 0, as jv_first_step */
   int jvx_last_step[THIP_MAX_JVX];
   double jvx_coeffs[THIP_MAX_JVX][THIP_MAX_DOF];
   double jvx_targets[THIP_MAX_JVX][THIP_MAX_DOF];
@@ -391,7 +391,7 @@ typedef struct thip_problem_desc {
   int coll_is_cnt;
   int coll_first_step;
   int coll_last_step;
-  int coll_n_fixed;
+  int coll_n_fixed;        /* thip_create and thip_terms_create refuse a value outside [0, THIP_MAX_STEPS] */
   int coll_fixed_steps[THIP_MAX_STEPS];
   double coll_margin;      /* dist_pen */
   double coll_coeff;       /* coeffs */

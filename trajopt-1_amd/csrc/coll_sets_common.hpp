@@ -19,9 +19,8 @@
 #include <string>
 #include <vector>
 
+#include "desc_lowering.hpp"
 #include "kin_device.hpp"
-#include "pair_data.hpp"
-#include "self_pairs.hpp"
 
 namespace thip
 {
@@ -81,17 +80,16 @@ using Reject = std::function<int(const std::string&)>;
 template <class Cfg>
 inline int check_descriptor(const thip_problem_desc& desc, const Cfg& cfg, const Reject& reject)
 {
-  if (desc.abi_version != THIP_ABI_VERSION)
-    return reject("descriptor abi_version " + std::to_string(desc.abi_version) + " != THIP_ABI_VERSION " +
-                  std::to_string(THIP_ABI_VERSION));
+  {
+    const std::string why = lowering::abi_mismatch(desc);
+    if (!why.empty())
+      return reject(why);
+  }
   const thip_chain& ch = desc.chain;
-  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF || ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
-    return reject("chain out of range");
-  for (int k = 1; k < ch.n_links; ++k)
-    if ((ch.joint_type[k] < 0 || ch.joint_type[k] > 3) ||
-        (ch.joint_type[k] != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof)) ||
-        (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k)))
-      return reject("bad chain joint / parent table");
+  if (const char* why = lowering::chain_range_finding(ch))
+    return reject(why);
+  if (const char* why = lowering::chain_table_finding(ch))
+    return reject(why);
   if (desc.n_steps < 1 || desc.n_steps > THIP_EVAL_MAX_STEPS)
     return reject("n_steps out of range");
   if (desc.n_prims < 0 || desc.n_prims > THIP_EVAL_MAX_PRIMS)
@@ -176,9 +174,7 @@ inline void fill_model(const thip_problem_desc& desc, const std::vector<int>& ss
                        thip_chain& chain, Model& md)
 {
   chain = desc.chain;
-  if (!chain.is_tree)
-    for (int k = 0; k < THIP_MAX_LINKS; ++k)
-      chain.parent[k] = k > 0 ? k - 1 : 0;
+  lowering::fill_serial_parents(chain);
   md = Model();
   md.n_sph = desc.n_spheres;
   md.n_self_sph = static_cast<int>(ssa.size());

@@ -41,9 +41,8 @@
 #include <vector>
 
 #include "collision_device.hpp"
+#include "desc_lowering.hpp"
 #include "kin_device.hpp"
-#include "pair_data.hpp"
-#include "self_pairs.hpp"
 
 namespace thip
 {
@@ -917,20 +916,19 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
     g_eval_create_err = "thip_eval_create: " + m;
     return THIP_E_INVALID;
   };
-  if (desc->abi_version != THIP_ABI_VERSION)
-    return reject("descriptor abi_version " + std::to_string(desc->abi_version) + " != THIP_ABI_VERSION " +
-                  std::to_string(THIP_ABI_VERSION));
+  {
+    const std::string why = thip::lowering::abi_mismatch(*desc);
+    if (!why.empty())
+      return reject(why);
+  }
   const thip_chain& ch = desc->chain;
   const int N = desc->n_steps;
-  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF || ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
-    return reject("chain out of range");
+  if (const char* why = thip::lowering::chain_range_finding(ch))
+    return reject(why);
   if (N < 1 || N > THIP_EVAL_MAX_STEPS)
     return reject("n_steps out of range");
-  for (int k = 1; k < ch.n_links; ++k)
-    if ((ch.joint_type[k] < 0 || ch.joint_type[k] > 3) ||
-        (ch.joint_type[k] != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof)) ||
-        (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k)))
-      return reject("bad chain joint / parent table");
+  if (const char* why = thip::lowering::chain_table_finding(ch))
+    return reject(why);
   if (desc->n_cart < 0 || desc->n_cart > THIP_MAX_CART)
     return reject("n_cart out of range");
   for (int k = 0; k < desc->n_cart; ++k)
@@ -980,9 +978,7 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
   ev->device = device;
   ev->batch = batch;
   ev->desc = *desc;
-  if (!ev->desc.chain.is_tree)
-    for (int k = 0; k < THIP_MAX_LINKS; ++k)
-      ev->desc.chain.parent[k] = k > 0 ? k - 1 : 0;
+  thip::lowering::fill_serial_parents(ev->desc.chain);
   const thip_problem_desc& d = ev->desc;
   // collision terms: 0 = coll_*, k = coll_extra[k - 1]
   std::vector<Unit> units;
@@ -1022,23 +1018,7 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
   Spheres sp{};
   if (n_terms > 0)
   {
-    std::vector<int> order;
-    for (int s = 0; s < d.n_spheres; ++s)
-      order.push_back(s);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d.sphere_link[a] < d.sphere_link[b]; });
-    for (size_t k = 0; k < order.size(); ++k)
-    {
-      sp.sph_order[k] = order[k];
-      const int link = d.sphere_link[order[k]];
-      if (sp.n_groups == 0 || sp.grp_link[sp.n_groups - 1] != link)
-      {
-        sp.grp_link[sp.n_groups] = link;
-        sp.grp_s0[sp.n_groups] = static_cast<int>(k);
-        sp.grp_ns[sp.n_groups] = 0;
-        sp.n_groups++;
-      }
-      sp.grp_ns[sp.n_groups - 1]++;
-    }
+    thip::lowering::store_sphere_groups(thip::lowering::group_spheres_by_link(d), sp);
     std::vector<int> ssa, ssb, skp;
     const std::string why = thip::self_sphere_pairs(d, ssa, ssb, skp);
     if (!why.empty())

@@ -21,23 +21,24 @@
 // bitwise repeatable and do not depend on a problem's position in the batch.
 // fp64; kinematics and distances are kin_device.hpp's / collision_device.hpp's.
 //
-// Slots are numbered as thip_create numbers Layout::n_costs / n_cnts,
-// jacc_slot, coll_cost0 and Tables::term_slot / jpos_slot / jvx_slot /
-// coll_slot (number_slots below restates that numbering; tests pin it against
-// the solver's A_COST / A_VIOL).
+// The evaluator accepts the descriptors thip_create accepts and numbers its
+// slots as thip_create numbers Layout::n_costs / n_cnts, jacc_slot, coll_cost0
+// and Tables::term_slot / jpos_slot / jvx_slot / coll_slot: both validate with
+// desc_lowering.hpp's validate() and read one term plan (plan_terms(); tests pin
+// the numbering against the solver's A_COST / A_VIOL).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "collision_device.hpp"
+#include "desc_lowering.hpp"
 #include "kin_device.hpp"
 #include "layout.hpp"
-#include "pair_data.hpp"
-#include "self_pairs.hpp"
 
 namespace thip
 {
@@ -463,7 +464,6 @@ struct thip_terms
 {
   int device = 0, batch = 0;
   thip_problem_desc desc{};
-  Layout L{};  // the slot fields only
   Slots slots{};
   std::vector<thip_term_slot> table;
   thip_problem_desc* d_desc = nullptr;
@@ -495,321 +495,71 @@ static thread_local std::string g_terms_create_err;
 
 namespace
 {
-const char* const kHostLoop =
+const std::string kHostLoop =
     ": not lowered into the batched kernels -- evaluate such a problem on the host loop "
     "(sco::BasicTrustRegionSQP, Cost::value / Constraint::violation)";
 
-// The descriptors thip_create accepts (thip_api.hip validate(), restated: the
-// same tests in the same order), refused with a reason before any device call.
-std::string validate_terms(const thip_problem_desc* d)
+// The descriptors thip_create accepts are refused here with the same tests
+// (lowering::validate), before any device call; the evaluator's words for the
+// findings each entry point words itself
+const std::string kTermsWording[lowering::kFindingCount] = {
+  "",  // kAccepted
+  "",  // kRefused: the shared reason as it stands
+  "",  // kAbiVersion
+  kHostLoop,  // kStepsRange
+  "jvx terms are the tolerance forms: a term with zero tolerances goes in jv_*",  // kJvxZeroTols
+  "JointAcc / JointJerk terms other than the fused JointAccEqCost (non-fused jdt)" + kHostLoop,  // kJdtNotFused
+  "time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs" +
+      kHostLoop,  // kTimeOrFixedDofs
+  "CartVel terms (n_cvel > 0) run the generic path, its device evaluator thip_eval_cart_vel_all" +
+      kHostLoop,                                               // kCartVel
+  "more than one collision term (coll_extra)" + kHostLoop,    // kCollExtra
+  "collision: n_prims out of range (THIP_MAX_PRIMS)" + kHostLoop,  // kPrimsRange
+};
+
+template <class A>
+void copy_array(A& dst, const A& src)
 {
-  if (d->abi_version != THIP_ABI_VERSION)
-    return "descriptor abi_version " + std::to_string(d->abi_version) + " != THIP_ABI_VERSION " +
-           std::to_string(THIP_ABI_VERSION);
-  const thip_chain& ch = d->chain;
-  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF)
-    return "n_dof out of range";
-  if (ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
-    return "n_links out of range";
-  if (d->n_steps < 2 || d->n_steps > THIP_MAX_STEPS)
-    return "n_steps must be in [2, " + std::to_string(THIP_MAX_STEPS) + "]" + kHostLoop;
-  for (int k = 1; k < ch.n_links; ++k)
-  {
-    const int ty = ch.joint_type[k];
-    if (ty < 0 || ty > 3)
-      return "bad joint type";
-    if (ty != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof))
-      return "bad joint dof index";
-    if (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k))
-      return "bad parent link (links must be in tree order, 0 <= parent[k] < k)";
-  }
-  if (d->n_fixed < 0 || d->n_fixed > THIP_MAX_STEPS)
-    return "n_fixed out of range";
-  {
-    std::vector<int> seen(static_cast<size_t>(d->n_steps), 0);
-    for (int f = 0; f < d->n_fixed; ++f)
-    {
-      const int t = d->fixed_steps[f];
-      if (t < 0 || t >= d->n_steps)
-        return "Fixed timestep index is outside the bounds of the initial trajectory.";
-      if (seen[static_cast<size_t>(t)]++)
-        return "duplicate fixed timestep";
-    }
-  }
-  if (d->n_cart < 0 || d->n_cart > THIP_MAX_CART)
-    return "n_cart out of range";
-  for (int k = 0; k < d->n_cart; ++k)
-  {
-    if (d->cart_step[k] < 0 || d->cart_step[k] >= d->n_steps)
-      return "CartPose timestep out of range";
-    if (d->cart_source_link[k] <= 0 || d->cart_source_link[k] >= ch.n_links)
-      return "CartPose source frame must be an active chain link";
-    if (d->cart_target_link[k] < 0 || d->cart_target_link[k] >= ch.n_links)
-      return "CartPose target link out of range (0: the static chain root)";
-  }
-  if (d->n_jvx < 0 || d->n_jvx > THIP_MAX_JVX)
-    return "n_jvx out of range";
-  for (int x = 0; x < d->n_jvx; ++x)
-  {
-    bool tol = false;
-    for (int j = 0; j < ch.n_dof; ++j)
-      tol = tol || std::fabs(d->jvx_upper_tols[x][j]) >= 1e-5 || std::fabs(d->jvx_lower_tols[x][j]) >= 1e-5;
-    if (!tol)
-      return "jvx terms are the tolerance forms: a term with zero tolerances goes in jv_*";
-  }
-  if (!thip_jdt_fused(d))
-    return std::string("JointAcc / JointJerk terms other than the fused JointAccEqCost (non-fused jdt)") + kHostLoop;
-  for (int k = 0; k < d->n_jdt; ++k)
-    if (d->jdt_first_step[k] < 0 || d->jdt_first_step[k] + 2 > d->jdt_last_step[k] ||
-        d->jdt_last_step[k] > d->n_steps - 1)
-      return "jdt term " + std::to_string(k) + ": need 0 <= jdt_first_step and jdt_first_step + 2 <= "
-             "jdt_last_step <= n_steps - 1 (got " + std::to_string(d->jdt_first_step[k]) + ", " +
-             std::to_string(d->jdt_last_step[k]) + " on " + std::to_string(d->n_steps) + " waypoints)";
-  if (d->use_time != 0 || d->n_jvt != 0 || d->n_ttt != 0 || d->n_fixed_dofs != 0)
-    return std::string("time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs") +
-           kHostLoop;
-  if (d->n_cvel != 0)
-    return std::string("CartVel terms (n_cvel > 0) run the generic path, its device evaluator thip_eval_cart_vel_all") +
-           kHostLoop;
-  if (d->coll_enabled && d->coll_contact_test != THIP_CONTACT_ALL && d->coll_contact_test != THIP_CONTACT_FIRST &&
-      d->coll_contact_test != THIP_CONTACT_CLOSEST)
-    return "coll_contact_test is not a THIP_CONTACT_* value";
-  if (d->n_coll_extra != 0)
-    return std::string("more than one collision term (coll_extra)") + kHostLoop;
-  if (d->n_jpos < 0 || d->n_jpos > THIP_MAX_JPOS)
-    return "n_jpos out of range";
-  for (int k = 0; k < d->n_jpos; ++k)
-    for (int j = 0; j < ch.n_dof; ++j)
-      if (!std::isfinite(d->jpos_coeffs[k][j]) || !std::isfinite(d->jpos_targets[k][j]) ||
-          !std::isfinite(d->jpos_upper_tols[k][j]) || !std::isfinite(d->jpos_lower_tols[k][j]))
-        return "JointPos coeffs / targets / tolerances must be finite";
-  if (d->coll_enabled)
-  {
-    if (d->n_spheres < 1 || d->n_spheres > THIP_MAX_SPHERES)
-      return "collision: n_spheres out of range";
-    for (int s = 0; s < d->n_spheres; ++s)
-      if (d->sphere_link[s] < 1 || d->sphere_link[s] >= ch.n_links || !(d->sphere_radius[s] >= 0))
-        return "collision: bad robot sphere";
-    if (d->n_prims < 0 || d->n_prims > THIP_MAX_PRIMS)
-      return std::string("collision: n_prims out of range (THIP_MAX_PRIMS)") + kHostLoop;
-    const int last = d->coll_last_step < 0 ? d->n_steps - 1 : d->coll_last_step;
-    if (d->coll_first_step < 0 || d->coll_first_step >= d->n_steps || last < d->coll_first_step || last >= d->n_steps)
-      return "collision: bad first/last step";
-    if (d->coll_continuous < 0 || d->coll_continuous > 2)
-      return "collision: coll_continuous must be 0 (LVS_DISCRETE), 1 (LVS_CONTINUOUS) or 2 (DISCRETE)";
-    const bool single = d->coll_continuous == 2;
-    if ((!single && !(d->coll_lvs > 0)) || !(d->coll_buffer >= 0))
-      return "collision: bad longest_valid_segment_length / buffer";
-    if (d->coll_n_fixed < 0 || d->coll_n_fixed > THIP_MAX_STEPS)
-      return "collision: coll_n_fixed out of range";
-    for (int t = d->coll_first_step; !single && t < last; ++t)
-    {
-      bool a = false, b = false;
-      for (int k = 0; k < d->coll_n_fixed; ++k)
-      {
-        a |= d->coll_fixed_steps[k] == t;
-        b |= d->coll_fixed_steps[k] == t + 1;
-      }
-      if (a && b)
-        return "Currently two adjacent fixed steps are not supported in collision term.";
-    }
-  }
-  for (int k = 0; k < d->n_cart; ++k)
-    if (d->cart_has_tol[k])
-      for (int i = 0; i < 6; ++i)
-        if (!(d->cart_lower_tol[k][i] <= d->cart_upper_tol[k][i]))
-          return "CartPoseErrCalculator: Inverted tolerance band - lower > upper at one or more indices";
-  if (d->coll_enabled && (d->coll_max_contacts < 0 || d->coll_max_contacts > THIP_MAX_CONTACTS))
-    return "collision: coll_max_contacts out of range";
-  if (d->coll_enabled)
-  {
-    std::vector<int> sa, sb, kp;
-    const std::string w = self_sphere_pairs(*d, sa, sb, kp);
-    if (!w.empty())
-      return w;
-  }
-  {
-    const std::string w = validate_coll_pairs(*d);
-    if (!w.empty())
-      return w;
-  }
-  // (the evaluator reads neither, but its domain is thip_create's)
-  if (!(d->sqp.max_time >= 0))
-    return "sqp.max_time must be >= 0 (DBL_MAX: no limit)";
-  if (!(d->sqp.trust_shrink_ratio > 0 && d->sqp.trust_shrink_ratio < 1) || !(d->sqp.min_trust_box_size > 0) ||
-      !(d->sqp.trust_box_size > 0))
-    return "sqp: need 0 < trust_shrink_ratio < 1, min_trust_box_size > 0 and trust_box_size > 0";
-  if (d->osqp.check_termination < 0 || d->osqp.max_iter < 1 || d->osqp.scaling < 0)
-    return "bad OSQP settings";
-  return "";
+  std::memcpy(&dst, &src, sizeof(A));
 }
 
-// thip_create's slot numbering (thip_api.hip:357-589) into Layout's slot fields,
-// the kernels' tables and the public slot table
-void number_slots(const thip_problem_desc& d, Layout& L, Slots& S, std::vector<thip_term_slot>& table)
+// the term plan (desc_lowering.hpp) as the kernels read it
+void fill_slots(const thip_problem_desc& d, const lowering::TermPlan& P, Slots& S)
 {
-  L.N = d.n_steps;
-  L.D = d.chain.n_dof;
-  L.n_cart = d.n_cart;
-  // JointVelTermInfo::hatch step clamping (problem_description.cpp:1228-1245)
-  auto jv_clamp = [&](int first, int last, int& f_out, int& l_out) {
-    if (last <= -1)
-      last = L.N - 1;
-    if ((L.N - 2) <= first)
-      first = L.N - 2;
-    if ((L.N - 1) <= last)
-      last = L.N - 1;
-    if (last == first)
-      last += 1;
-    if (last < first)
-      std::swap(first, last);
-    f_out = first;
-    l_out = last;
-  };
-  jv_clamp(d.jv_first_step, d.jv_last_step, L.jv_first, L.jv_last);
-  for (int x = 0; x < d.n_jvx; ++x)
-    jv_clamp(d.jvx_first_step[x], d.jvx_last_step[x], S.jvx_first[x], S.jvx_last[x]);
-  L.n_jvx = d.n_jvx;
-  auto zero_tol = [](double v) { return std::fabs(v) < 1e-5; };
-  L.jv_ineq = 0;
-  if (d.jv_enabled)
-    for (int j = 0; j < L.D; ++j)
-      if (!zero_tol(d.jv_upper_tols[j]) || !zero_tol(d.jv_lower_tols[j]))
-        L.jv_ineq = 1;
-  for (int k = 0; k < d.n_jpos; ++k)
-    for (int j = 0; j < L.D; ++j)
-      if (!zero_tol(d.jpos_upper_tols[k][j]) || !zero_tol(d.jpos_lower_tols[k][j]))
-        S.jpos_ineq[k] = 1;
-  std::vector<thip_term_slot> cost_tab, cnt_tab;
-  auto entry = [](int kind, int index, int unit, int is_cnt) {
-    thip_term_slot e;
-    e.kind = kind;
-    e.index = index;
-    e.unit = unit;
-    e.is_cnt = is_cnt;
-    return e;
-  };
-  int n_costs = 0, n_cnts = 0;
-  if (d.jv_enabled)
-  {
-    cost_tab.push_back(entry(THIP_TERM_JOINT_VEL, 0, -1, 0));
-    n_costs = 1;
-  }
-  // CartPose terms: cost terms first, then constraint terms, each in descriptor order
-  for (int pass = 0; pass < 2; ++pass)
-    for (int k = 0; k < d.n_cart; ++k)
-    {
-      if ((pass == 0) != (d.cart_is_cnt[k] == 0))
-        continue;
-      int nr = 0;
-      for (int i = 0; i < 6; ++i)
-      {
-        const double cf = (i < 3) ? d.cart_pos_coeffs[k][i] : d.cart_rot_coeffs[k][i - 3];
-        if (std::fabs(cf) > 1e-5)
-        {
-          S.row_comp[k][nr] = i;
-          S.row_w[k][nr] = cf;
-          nr++;
-        }
-      }
-      S.term_nrow[k] = nr;
-      S.term_slot[k] = (pass == 0) ? n_costs++ : n_cnts++;
-      (pass == 0 ? cost_tab : cnt_tab).push_back(entry(THIP_TERM_CART, k, -1, pass));
-    }
-  // JointPosTermInfo::hatch step clamping (problem_description.cpp:1097-1196)
-  L.n_jpos = d.n_jpos;
-  for (int k = 0; k < d.n_jpos; ++k)
-  {
-    int f = d.jpos_first_step[k], l = d.jpos_last_step[k];
-    if (l <= -1)
-      l = L.N - 1;
-    if ((L.N - 1) <= f)
-      f = L.N - 1;
-    if ((L.N - 1) <= l)
-      l = L.N - 1;
-    if (l < f)
-      std::swap(f, l);
-    f = std::max(f, 0);
-    S.jpos_first[k] = f;
-    S.jpos_last[k] = l;
-    if (!d.jpos_is_cnt[k])
-    {
-      S.jpos_slot[k] = n_costs++;
-      cost_tab.push_back(entry(THIP_TERM_JPOS, k, -1, 0));
-    }
-  }
-  for (int x = 0; x < d.n_jvx; ++x)
-    if (!d.jvx_is_cnt[x])
-    {
-      S.jvx_slot[x] = n_costs++;
-      cost_tab.push_back(entry(THIP_TERM_JVX, x, -1, 0));
-    }
-  L.n_jacc = d.n_jdt;
-  for (int k = 0; k < THIP_MAX_JDT; ++k)
-  {
-    L.jacc_slot[k] = (k < d.n_jdt) ? n_costs++ : -1;
-    if (k < d.n_jdt)
-      cost_tab.push_back(entry(THIP_TERM_JDT, k, -1, 0));
-  }
-  for (int k = 0; k < d.n_jpos; ++k)
-    if (d.jpos_is_cnt[k])
-    {
-      S.jpos_slot[k] = n_cnts++;
-      cnt_tab.push_back(entry(THIP_TERM_JPOS, k, -1, 1));
-    }
-  for (int x = 0; x < d.n_jvx; ++x)
-    if (d.jvx_is_cnt[x])
-    {
-      S.jvx_slot[x] = n_cnts++;
-      cnt_tab.push_back(entry(THIP_TERM_JVX, x, -1, 1));
-    }
-  // collision: one term per unit after the other costs (or constraints)
-  L.coll = d.coll_enabled ? 1 : 0;
-  L.coll_first = d.coll_first_step;
-  L.coll_last = (d.coll_last_step < 0) ? L.N - 1 : d.coll_last_step;
-  L.coll_single = (L.coll && d.coll_continuous == 2) ? 1 : 0;
-  if (L.coll_single)
-    L.coll_last += 1;
-  L.coll_cnt = (L.coll && d.coll_is_cnt) ? 1 : 0;
-  L.coll_cost0 = L.coll_cnt ? n_cnts : n_costs;
-  int n_units = 0;
-  for (int k = 0; L.coll && k < d.coll_n_fixed; ++k)
-    if (d.coll_fixed_steps[k] >= 0 && d.coll_fixed_steps[k] < L.N)
-      S.coll_fixed[d.coll_fixed_steps[k]] = 1;
-  for (int t = L.coll_first; L.coll && t < L.coll_last; ++t)
-    if (!(L.coll_single && S.coll_fixed[t]))
-    {
-      S.unit_t[n_units] = t;
-      S.unit_slot[n_units] = n_units;
-      (L.coll_cnt ? cnt_tab : cost_tab).push_back(entry(THIP_TERM_COLL, n_units, t, L.coll_cnt));
-      n_units++;
-    }
-  if (L.coll)
-    (L.coll_cnt ? n_cnts : n_costs) += n_units;
-  L.n_costs = n_costs;
-  L.n_cnts = n_cnts;
-
-  S.N = L.N;
-  S.D = L.D;
-  S.n_costs = L.n_costs;
-  S.n_cnts = L.n_cnts;
-  S.jv_eq = (d.jv_enabled && !L.jv_ineq) ? 1 : 0;
-  S.jv_ineq = L.jv_ineq;
-  S.jv_first = L.jv_first;
-  S.jv_last = L.jv_last;
-  S.n_jacc = L.n_jacc;
-  for (int k = 0; k < THIP_MAX_JDT; ++k)
-    S.jacc_slot[k] = L.jacc_slot[k];
-  S.n_cart = L.n_cart;
-  S.n_jpos = L.n_jpos;
-  S.n_jvx = L.n_jvx;
-  S.coll = L.coll;
-  S.coll_single = L.coll_single;
-  S.coll_cnt = L.coll_cnt;
-  S.coll_cost0 = L.coll_cost0;
-  S.n_units = n_units;
-  table = cost_tab;
-  table.insert(table.end(), cnt_tab.begin(), cnt_tab.end());
+  S = Slots{};
+  S.N = P.N;
+  S.D = P.D;
+  S.n_costs = P.n_costs;
+  S.n_cnts = P.n_cnts;
+  S.jv_eq = (d.jv_enabled && !P.jv_ineq) ? 1 : 0;
+  S.jv_ineq = P.jv_ineq;
+  S.jv_first = P.jv_first;
+  S.jv_last = P.jv_last;
+  S.n_jacc = d.n_jdt;
+  copy_array(S.jacc_slot, P.jacc_slot);
+  S.n_cart = d.n_cart;
+  copy_array(S.term_nrow, P.cart_nrow);
+  copy_array(S.term_slot, P.cart_slot);
+  copy_array(S.row_comp, P.cart_comp);
+  copy_array(S.row_w, P.cart_w);
+  S.n_jpos = d.n_jpos;
+  copy_array(S.jpos_first, P.jpos_first);
+  copy_array(S.jpos_last, P.jpos_last);
+  copy_array(S.jpos_slot, P.jpos_slot);
+  copy_array(S.jpos_ineq, P.jpos_ineq);
+  S.n_jvx = d.n_jvx;
+  copy_array(S.jvx_first, P.jvx_first);
+  copy_array(S.jvx_last, P.jvx_last);
+  copy_array(S.jvx_slot, P.jvx_slot);
+  S.coll = P.coll;
+  S.coll_single = P.coll_single;
+  S.coll_cnt = P.coll_cnt;
+  S.coll_cost0 = P.coll_cost0;
+  S.n_units = P.n_units;
+  copy_array(S.unit_t, P.unit_t);
+  for (int u = 0; u < P.n_units; ++u)
+    S.unit_slot[u] = u;
+  copy_array(S.coll_fixed, P.coll_fixed);
 }
 
 int tfail(thip_terms* t, const std::string& m)
@@ -980,19 +730,22 @@ int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip
     return THIP_E_INVALID;
   };
   {
-    const std::string why = validate_terms(desc);
-    if (!why.empty())
-      return reject(why);
+    std::string why;
+    if (const lowering::Finding f = lowering::validate(*desc, why))
+      return reject(why + kTermsWording[f]);
   }
   auto* t = new thip_terms();
   t->device = device;
   t->batch = batch;
   t->desc = *desc;
-  if (!t->desc.chain.is_tree)  // serial chain: parent[] is not read from the caller
-    for (int k = 0; k < THIP_MAX_LINKS; ++k)
-      t->desc.chain.parent[k] = k > 0 ? k - 1 : 0;
+  lowering::fill_serial_parents(t->desc.chain);
   const thip_problem_desc& d = t->desc;
-  number_slots(d, t->L, t->slots, t->table);
+  {
+    lowering::TermPlan P;
+    lowering::plan_terms(d, P);
+    fill_slots(d, P, t->slots);
+    t->table = P.table;
+  }
   const Slots& S = t->slots;
   if (static_cast<long long>(std::max(S.n_units, 1)) * batch > INT_MAX)
   {
@@ -1003,26 +756,11 @@ int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip
   std::vector<double> ptab;
   if (d.coll_enabled)
   {
-    std::vector<int> order, ssa, ssb, skp;
+    std::vector<int> ssa, ssb, skp;
     self_sphere_pairs(d, ssa, ssb, skp);
-    for (int s = 0; s < d.n_spheres; ++s)
-      order.push_back(s);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d.sphere_link[a] < d.sphere_link[b]; });
     md.n_sph = d.n_spheres;
     md.n_prims = d.n_prims;
-    for (size_t k = 0; k < order.size(); ++k)
-    {
-      md.sph_order[k] = order[k];
-      const int link = d.sphere_link[order[k]];
-      if (md.n_groups == 0 || md.grp_link[md.n_groups - 1] != link)
-      {
-        md.grp_link[md.n_groups] = link;
-        md.grp_s0[md.n_groups] = static_cast<int>(k);
-        md.grp_ns[md.n_groups] = 0;
-        md.n_groups++;
-      }
-      md.grp_ns[md.n_groups - 1]++;
-    }
+    lowering::store_sphere_groups(lowering::group_spheres_by_link(d), md);
     md.n_self_sph = static_cast<int>(ssa.size());
     for (size_t j = 0; j < ssa.size(); ++j)
     {
@@ -1120,22 +858,20 @@ int thip_terms_slot_table(const thip_problem_desc* desc, thip_term_slot* out, in
     g_terms_create_err = "thip_terms_slot_table: bad arguments";
     return THIP_E_INVALID;
   }
-  const std::string why = validate_terms(desc);
-  if (!why.empty())
+  std::string why;
+  if (const lowering::Finding f = lowering::validate(*desc, why))
   {
-    g_terms_create_err = "thip_terms_slot_table: " + why;
+    g_terms_create_err = "thip_terms_slot_table: " + why + kTermsWording[f];
     return THIP_E_INVALID;
   }
-  Layout L{};
-  Slots S{};
-  std::vector<thip_term_slot> table;
-  number_slots(*desc, L, S, table);
+  lowering::TermPlan P;
+  lowering::plan_terms(*desc, P);
   if (n_costs)
-    *n_costs = L.n_costs;
+    *n_costs = P.n_costs;
   if (n_cnts)
-    *n_cnts = L.n_cnts;
-  for (size_t k = 0; k < table.size() && k < static_cast<size_t>(cap); ++k)
-    out[k] = table[k];
+    *n_cnts = P.n_cnts;
+  for (size_t k = 0; k < P.table.size() && k < static_cast<size_t>(cap); ++k)
+    out[k] = P.table[k];
   return THIP_OK;
 }
 

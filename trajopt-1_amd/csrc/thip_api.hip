@@ -15,9 +15,8 @@
 #include <cstdlib>
 #include <functional>
 
+#include "desc_lowering.hpp"
 #include "layout.hpp"
-#include "pair_data.hpp"
-#include "self_pairs.hpp"
 
 namespace thip
 {
@@ -155,189 +154,29 @@ int thip_debug_set_path(int flags)
   return THIP_OK;
 }
 
-extern "C" int thip_jdt_fused(const thip_problem_desc* d)
-{
-  int k, j;
-  if (d->n_jdt == 0)
-    return 1;
-  if (d->n_jdt < 0 || d->n_jdt > THIP_MAX_JDT || d->n_steps % 2 != 0 || 2 * d->chain.n_dof > THIP_MAX_DOF ||
-      d->use_time)
-    return 0;
-  for (k = 0; k < d->n_jdt; ++k)
-  {
-    if (d->jdt_order[k] != 2 || d->jdt_is_cnt[k])
-      return 0;
-    for (j = 0; j < d->chain.n_dof; ++j)
-      if (d->jdt_upper_tols[k][j] >= 1e-5 || d->jdt_upper_tols[k][j] <= -1e-5 || d->jdt_lower_tols[k][j] >= 1e-5 ||
-          d->jdt_lower_tols[k][j] <= -1e-5)
-        return 0;
-  }
-  return 1;
-}
+int thip_jdt_fused(const thip_problem_desc* d) { return lowering::jdt_fused(*d) ? 1 : 0; }
 
-static int validate(const thip_problem_desc* d, std::string& why)
-{
-  if (d->abi_version != THIP_ABI_VERSION)
-    return why = "descriptor abi_version " + std::to_string(d->abi_version) + " != THIP_ABI_VERSION " +
-                 std::to_string(THIP_ABI_VERSION) + " (caller built against another trajopt_hip.h)",
-           THIP_E_INVALID;
-  const thip_chain& ch = d->chain;
-  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF)
-    return why = "n_dof out of range", THIP_E_INVALID;
-  if (ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
-    return why = "n_links out of range", THIP_E_INVALID;
-  if (d->n_steps < 2 || d->n_steps > THIP_MAX_STEPS)
-    return why = "n_steps must be in [2, " + std::to_string(THIP_MAX_STEPS) +
-                 "] for the batched kernel (single-waypoint problems run sco::BasicTrustRegionSQP's generic path)",
-           THIP_E_INVALID;
-  for (int k = 1; k < ch.n_links; ++k)
-  {
-    const int ty = ch.joint_type[k];
-    if (ty < 0 || ty > 3)
-      return why = "bad joint type", THIP_E_INVALID;
-    if (ty != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof))
-      return why = "bad joint dof index", THIP_E_INVALID;
-    if (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k))
-      return why = "bad parent link (links must be in tree order, 0 <= parent[k] < k)", THIP_E_INVALID;
-  }
-  if (d->n_fixed < 0 || d->n_fixed > THIP_MAX_STEPS)
-    return why = "n_fixed out of range", THIP_E_INVALID;
-  std::vector<int> seen(static_cast<size_t>(d->n_steps), 0);
-  for (int f = 0; f < d->n_fixed; ++f)
-  {
-    const int t = d->fixed_steps[f];
-    if (t < 0 || t >= d->n_steps)
-      return why = "Fixed timestep index is outside the bounds of the initial trajectory.", THIP_E_INVALID;
-    if (seen[static_cast<size_t>(t)]++)
-      return why = "duplicate fixed timestep", THIP_E_INVALID;
-  }
-  if (d->n_cart < 0 || d->n_cart > THIP_MAX_CART)
-    return why = "n_cart out of range", THIP_E_INVALID;
-  for (int k = 0; k < d->n_cart; ++k)
-  {
-    if (d->cart_step[k] < 0 || d->cart_step[k] >= d->n_steps)
-      return why = "CartPose timestep out of range", THIP_E_INVALID;
-    if (d->cart_source_link[k] <= 0 || d->cart_source_link[k] >= ch.n_links)
-      return why = "CartPose source frame must be an active chain link", THIP_E_INVALID;
-    if (d->cart_target_link[k] < 0 || d->cart_target_link[k] >= ch.n_links)
-      return why = "CartPose target link out of range (0: the static chain root)", THIP_E_INVALID;
-  }
-  if (d->n_jvx < 0 || d->n_jvx > THIP_MAX_JVX)
-    return why = "n_jvx out of range", THIP_E_INVALID;
-  for (int x = 0; x < d->n_jvx; ++x)
-  {
-    bool tol = false;
-    for (int j = 0; j < d->chain.n_dof; ++j)
-      tol = tol || std::fabs(d->jvx_upper_tols[x][j]) >= 1e-5 || std::fabs(d->jvx_lower_tols[x][j]) >= 1e-5;
-    if (!tol)
-      return why = "jvx terms are the tolerance forms (JointVelIneqCost / JointVelIneqConstraint): "
-                   "a term with zero tolerances goes in jv_*",
-             THIP_E_INVALID;
-  }
-  if (!thip_jdt_fused(d))
-    return why = "JointAcc / JointJerk terms other than JointAccEqCost on an even number of waypoints with "
-                 "2 n_dof <= THIP_MAX_DOF, and JointVel equality constraints, are not lowered into the batched "
-                 "kernel: solve such a problem with sco::BasicTrustRegionSQP (the generic path, GpuModel)",
-           THIP_E_INVALID;
-  // the kernels index x with a JointAccEqCost term's steps as given (jacc_value,
-  // build_and_scale, term_values.hip): the range JointAccTermInfo::hatch clamps to
-  for (int k = 0; k < d->n_jdt; ++k)
-    if (d->jdt_first_step[k] < 0 || d->jdt_first_step[k] + 2 > d->jdt_last_step[k] ||
-        d->jdt_last_step[k] > d->n_steps - 1)
-      return why = "jdt term " + std::to_string(k) + ": need 0 <= jdt_first_step and jdt_first_step + 2 <= "
-                   "jdt_last_step <= n_steps - 1 (got " + std::to_string(d->jdt_first_step[k]) + ", " +
-                   std::to_string(d->jdt_last_step[k]) + " on " + std::to_string(d->n_steps) + " waypoints)",
-             THIP_E_INVALID;
-  if (d->use_time != 0 || d->n_jvt != 0 || d->n_ttt != 0 || d->n_fixed_dofs != 0)
-    return why = "time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs are not "
-                 "lowered into the batched kernel: solve such a problem with sco::BasicTrustRegionSQP (the generic "
-                 "path, GpuModel)",
-           THIP_E_INVALID;
-  if (d->n_cvel != 0)
-    return why = "CartVel terms (n_cvel > 0) are not lowered into the batched kernel: solve such a problem with "
-                 "sco::BasicTrustRegionSQP (the generic path, device-evaluated terms and GpuModel)",
-           THIP_E_INVALID;
-  if (d->coll_enabled && d->coll_contact_test != THIP_CONTACT_ALL && d->coll_contact_test != THIP_CONTACT_FIRST &&
-      d->coll_contact_test != THIP_CONTACT_CLOSEST)
-    return why = "coll_contact_test is not a THIP_CONTACT_* value", THIP_E_INVALID;
-  if (d->n_coll_extra != 0)
-    return why = "more than one collision term is not lowered into the batched kernel: solve such a problem with "
-                 "sco::BasicTrustRegionSQP (the generic path, device-evaluated terms and GpuModel)",
-           THIP_E_INVALID;
-  if (d->n_jpos < 0 || d->n_jpos > THIP_MAX_JPOS)
-    return why = "n_jpos out of range", THIP_E_INVALID;
-  for (int k = 0; k < d->n_jpos; ++k)
-    for (int j = 0; j < ch.n_dof; ++j)
-    {
-      if (!std::isfinite(d->jpos_coeffs[k][j]) || !std::isfinite(d->jpos_targets[k][j]) ||
-          !std::isfinite(d->jpos_upper_tols[k][j]) || !std::isfinite(d->jpos_lower_tols[k][j]))
-        return why = "JointPos coeffs / targets / tolerances must be finite", THIP_E_INVALID;
-    }
-  if (d->coll_enabled)
-  {
-    if (d->n_spheres < 1 || d->n_spheres > THIP_MAX_SPHERES)
-      return why = "collision: n_spheres out of range", THIP_E_INVALID;
-    for (int s = 0; s < d->n_spheres; ++s)
-      if (d->sphere_link[s] < 1 || d->sphere_link[s] >= ch.n_links || !(d->sphere_radius[s] >= 0))
-        return why = "collision: bad robot sphere", THIP_E_INVALID;
-    if (d->n_prims < 0 || d->n_prims > THIP_MAX_PRIMS)
-      return why = "collision: n_prims out of range", THIP_E_INVALID;
-    const int last = d->coll_last_step < 0 ? d->n_steps - 1 : d->coll_last_step;
-    if (d->coll_first_step < 0 || d->coll_first_step >= d->n_steps || last < d->coll_first_step ||
-        last >= d->n_steps)
-      return why = "collision: bad first/last step", THIP_E_INVALID;
-    if (d->coll_continuous < 0 || d->coll_continuous > 2)
-      return why = "collision: coll_continuous must be 0 (LVS_DISCRETE), 1 (LVS_CONTINUOUS) or 2 (DISCRETE)",
-             THIP_E_INVALID;
-    const bool single = d->coll_continuous == 2;
-    if (single && d->n_steps < 2)
-      return why = "collision: DISCRETE needs at least 2 waypoints", THIP_E_INVALID;
-    if ((!single && !(d->coll_lvs > 0)) || !(d->coll_buffer >= 0))
-      return why = "collision: bad longest_valid_segment_length / buffer", THIP_E_INVALID;
-    // (single-timestep terms skip fixed waypoints; only the step-pair evaluators reject
-    // adjacent fixed steps, problem_description.cpp:1765-1767 vs :1785-1795)
-    for (int t = d->coll_first_step; !single && t < last; ++t)
-    {
-      bool a = false, b = false;
-      for (int k = 0; k < d->coll_n_fixed; ++k)
-      {
-        a |= d->coll_fixed_steps[k] == t;
-        b |= d->coll_fixed_steps[k] == t + 1;
-      }
-      if (a && b)
-        return why = "Currently two adjacent fixed steps are not supported in collision term.", THIP_E_INVALID;
-    }
-  }
-  for (int k = 0; k < d->n_cart; ++k)
-    if (d->cart_has_tol[k])
-      for (int i = 0; i < 6; ++i)
-        if (!(d->cart_lower_tol[k][i] <= d->cart_upper_tol[k][i]))
-          return why = "CartPoseErrCalculator: Inverted tolerance band - lower > upper at one or more indices",
-                 THIP_E_INVALID;
-  if (d->coll_enabled && (d->coll_max_contacts < 0 || d->coll_max_contacts > THIP_MAX_CONTACTS))
-    return why = "collision: coll_max_contacts out of range", THIP_E_INVALID;
-  if (d->coll_enabled)
-  {
-    std::vector<int> sa, sb, kp;
-    const std::string w = self_sphere_pairs(*d, sa, sb, kp);
-    if (!w.empty())
-      return why = w, THIP_E_INVALID;
-  }
-  {
-    const std::string w = validate_coll_pairs(*d);
-    if (!w.empty())
-      return why = w, THIP_E_INVALID;
-  }
-  if (!(d->sqp.max_time >= 0))
-    return why = "sqp.max_time must be >= 0 (DBL_MAX: no limit)", THIP_E_INVALID;
-  if (!(d->sqp.trust_shrink_ratio > 0 && d->sqp.trust_shrink_ratio < 1) || !(d->sqp.min_trust_box_size > 0) ||
-      !(d->sqp.trust_box_size > 0))
-    return why = "sqp: need 0 < trust_shrink_ratio < 1, min_trust_box_size > 0 and trust_box_size > 0",
-           THIP_E_INVALID;
-  if (d->osqp.check_termination < 0 || d->osqp.max_iter < 1 || d->osqp.scaling < 0)
-    return why = "bad OSQP settings", THIP_E_INVALID;
-  return THIP_OK;
-}
+// thip_create's words for the findings of lowering::validate() that each entry point words itself
+static const char* const kCreateWording[lowering::kFindingCount] = {
+  "",  // kAccepted
+  "",  // kRefused: the shared reason as it stands
+  " (caller built against another trajopt_hip.h)",  // kAbiVersion
+  // kStepsRange, kJvxZeroTols, kJdtNotFused, kTimeOrFixedDofs, kCartVel, kCollExtra, kPrimsRange:
+  " for the batched kernel (single-waypoint problems run sco::BasicTrustRegionSQP's generic path)",
+  "jvx terms are the tolerance forms (JointVelIneqCost / JointVelIneqConstraint): "
+  "a term with zero tolerances goes in jv_*",
+  "JointAcc / JointJerk terms other than JointAccEqCost on an even number of waypoints with "
+  "2 n_dof <= THIP_MAX_DOF, and JointVel equality constraints, are not lowered into the batched "
+  "kernel: solve such a problem with sco::BasicTrustRegionSQP (the generic path, GpuModel)",
+  "time-parameterised problems (use_time, JointVel terms with use_time, TotalTime) and fixed dofs are not "
+  "lowered into the batched kernel: solve such a problem with sco::BasicTrustRegionSQP (the generic "
+  "path, GpuModel)",
+  "CartVel terms (n_cvel > 0) are not lowered into the batched kernel: solve such a problem with "
+  "sco::BasicTrustRegionSQP (the generic path, device-evaluated terms and GpuModel)",
+  "more than one collision term is not lowered into the batched kernel: solve such a problem with "
+  "sco::BasicTrustRegionSQP (the generic path, device-evaluated terms and GpuModel)",
+  "collision: n_prims out of range",
+};
 
 int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx** out)
 {
@@ -347,18 +186,16 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     return THIP_E_INVALID;
   }
   std::string why;
-  if (validate(desc, why) != THIP_OK)
+  if (const lowering::Finding f = lowering::validate(*desc, why))
   {
-    g_create_err = "thip_create: " + why;
+    g_create_err = "thip_create: " + why + kCreateWording[f];
     return THIP_E_INVALID;
   }
   auto* ctx = new thip_ctx();
   ctx->device = device;
   ctx->batch = batch;
   ctx->desc = *desc;
-  if (!ctx->desc.chain.is_tree)  // serial chain: parent[] is not read from the caller
-    for (int k = 0; k < THIP_MAX_LINKS; ++k)
-      ctx->desc.chain.parent[k] = k > 0 ? k - 1 : 0;
+  lowering::fill_serial_parents(ctx->desc.chain);
   const thip_problem_desc& d = ctx->desc;
   Layout& L = ctx->L;
   L.N = d.n_steps;
@@ -368,121 +205,56 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
   L.n_fixed = d.n_fixed;
   L.n_fixed_rows = d.n_fixed * L.D;
   L.n_cart = d.n_cart;
-  // JointVelTermInfo::hatch step clamping (problem_description.cpp:1228-1245)
-  auto jv_clamp = [&](int first, int last, int& f_out, int& l_out) {
-    if (last <= -1)
-      last = L.N - 1;
-    if ((L.N - 2) <= first)
-      first = L.N - 2;
-    if ((L.N - 1) <= last)
-      last = L.N - 1;
-    if (last == first)
-      last += 1;
-    if (last < first)
-      std::swap(first, last);
-    f_out = first;
-    l_out = last;
-  };
-  jv_clamp(d.jv_first_step, d.jv_last_step, L.jv_first, L.jv_last);
-  std::vector<int> jvx_first(THIP_MAX_JVX, 0), jvx_last(THIP_MAX_JVX, 0), jvx_slot(THIP_MAX_JVX, 0);
-  for (int x = 0; x < d.n_jvx; ++x)
-    jv_clamp(d.jvx_first_step[x], d.jvx_last_step[x], jvx_first[static_cast<size_t>(x)],
-             jvx_last[static_cast<size_t>(x)]);
+  // step ranges, kept components and slots: the term plan (desc_lowering.hpp)
+  lowering::TermPlan P;
+  lowering::plan_terms(d, P);
+  L.jv_first = P.jv_first;
+  L.jv_last = P.jv_last;
+  L.jv_ineq = P.jv_ineq;
   L.n_jvx = d.n_jvx;
-  // zero tolerances: trajopt_common::doubleEquals(tol, 0.) (problem_description.cpp:1135-1138,1249-1252)
-  auto zero_tol = [](double v) { return std::fabs(v) < 1e-5; };
-  L.jv_ineq = 0;
-  if (d.jv_enabled)
-    for (int j = 0; j < L.D; ++j)
-      if (!zero_tol(d.jv_upper_tols[j]) || !zero_tol(d.jv_lower_tols[j]))
-        L.jv_ineq = 1;
-  std::vector<int> jpos_ineq(THIP_MAX_JPOS, 0);
-  for (int k = 0; k < d.n_jpos; ++k)
-    for (int j = 0; j < L.D; ++j)
-      if (!zero_tol(d.jpos_upper_tols[k][j]) || !zero_tol(d.jpos_lower_tols[k][j]))
-        jpos_ineq[static_cast<size_t>(k)] = 1;
-  // CartPose rows: cost terms first (convexifyCosts order), then constraint terms (cntsToCosts)
-  std::vector<int> row_term, row_comp, row_step, term_row0(THIP_MAX_CART, 0), term_nrow(THIP_MAX_CART, 0),
-      term_slot(THIP_MAX_CART, 0);
-  std::vector<double> row_w;
-  int n_costs = d.jv_enabled ? 1 : 0, n_cnts = 0;
-  for (int pass = 0; pass < 2; ++pass)
-    for (int k = 0; k < d.n_cart; ++k)
-    {
-      if ((pass == 0) != (d.cart_is_cnt[k] == 0))
-        continue;
-      term_row0[k] = static_cast<int>(row_term.size());
-      for (int i = 0; i < 6; ++i)
-      {
-        const double cf = (i < 3) ? d.cart_pos_coeffs[k][i] : d.cart_rot_coeffs[k][i - 3];
-        if (std::fabs(cf) > 1e-5)
-        {
-          row_term.push_back(k);
-          row_comp.push_back(i);
-          row_step.push_back(d.cart_step[k]);
-          row_w.push_back(cf);
-        }
-      }
-      term_nrow[k] = static_cast<int>(row_term.size()) - term_row0[k];
-      term_slot[k] = (pass == 0) ? n_costs++ : n_cnts++;
-    }
-  std::vector<int> row_slot, row_jpos(row_term.size(), 0);
-  for (size_t r = 0; r < row_term.size(); ++r)
-    row_slot.push_back(d.cart_is_cnt[row_term[r]] ? term_slot[static_cast<size_t>(row_term[r])] : -1);
-  // JointPosTermInfo::hatch (problem_description.cpp:1097-1196): step clamping; costs are
-  // quadratic (no rows), constraints add one EQ row per (step, joint) after the CartPose
-  // constraint rows (cnt_infos order, JointPosEqConstraint ctor order: step-major)
-  std::vector<int> jpos_first(THIP_MAX_JPOS, 0), jpos_last(THIP_MAX_JPOS, 0), jpos_slot(THIP_MAX_JPOS, 0),
-      jpos_row0(THIP_MAX_JPOS, 0), jpos_nrow(THIP_MAX_JPOS, 0);
   L.n_jpos = d.n_jpos;
-  for (int k = 0; k < d.n_jpos; ++k)
-  {
-    int f = d.jpos_first_step[k], l = d.jpos_last_step[k];
-    if (l <= -1)
-      l = L.N - 1;
-    if ((L.N - 1) <= f)
-      f = L.N - 1;
-    if ((L.N - 1) <= l)
-      l = L.N - 1;
-    if (l < f)
-      std::swap(f, l);
-    f = std::max(f, 0);
-    jpos_first[static_cast<size_t>(k)] = f;
-    jpos_last[static_cast<size_t>(k)] = l;
-    if (!d.jpos_is_cnt[k])
-      jpos_slot[static_cast<size_t>(k)] = n_costs++;
-  }
-  for (int x = 0; x < d.n_jvx; ++x)
-    if (!d.jvx_is_cnt[x])
-      jvx_slot[static_cast<size_t>(x)] = n_costs++;
-  // JointAccEqCost terms (thip_jdt_fused): cost slots after the JointVel
-  // tolerance costs (the oracle's / ConstructProblem's cost order)
   L.n_jacc = d.n_jdt;
   for (int k = 0; k < THIP_MAX_JDT; ++k)
-    L.jacc_slot[k] = (k < d.n_jdt) ? n_costs++ : -1;
+    L.jacc_slot[k] = P.jacc_slot[k];
+  const std::vector<int> jvx_first(P.jvx_first, P.jvx_first + THIP_MAX_JVX),
+      jvx_last(P.jvx_last, P.jvx_last + THIP_MAX_JVX), jvx_slot(P.jvx_slot, P.jvx_slot + THIP_MAX_JVX),
+      jpos_ineq(P.jpos_ineq, P.jpos_ineq + THIP_MAX_JPOS), jpos_first(P.jpos_first, P.jpos_first + THIP_MAX_JPOS),
+      jpos_last(P.jpos_last, P.jpos_last + THIP_MAX_JPOS), jpos_slot(P.jpos_slot, P.jpos_slot + THIP_MAX_JPOS),
+      term_nrow(P.cart_nrow, P.cart_nrow + THIP_MAX_CART), term_slot(P.cart_slot, P.cart_slot + THIP_MAX_CART);
+  // CartPose rows in the plan's order: cost terms first (convexifyCosts order), then
+  // constraint terms (cntsToCosts); a cost row has no merit slot
+  std::vector<int> row_term, row_comp, row_step, row_slot, row_jpos, term_row0(THIP_MAX_CART, 0);
+  std::vector<double> row_w;
+  auto add_row = [&](int term, int comp, int step, double w, int slot, int jpos) {
+    row_term.push_back(term);
+    row_comp.push_back(comp);
+    row_step.push_back(step);
+    row_w.push_back(w);
+    row_slot.push_back(slot);
+    row_jpos.push_back(jpos);
+  };
+  for (int e = 0; e < d.n_cart; ++e)
+  {
+    const int k = P.cart_order[e];
+    term_row0[static_cast<size_t>(k)] = static_cast<int>(row_term.size());
+    for (int i = 0; i < P.cart_nrow[k]; ++i)
+      add_row(k, P.cart_comp[k][i], d.cart_step[k], P.cart_w[k][i], d.cart_is_cnt[k] ? P.cart_slot[k] : -1, 0);
+  }
+  // JointPos terms (JointPosTermInfo::hatch, problem_description.cpp:1097-1196): costs are
+  // quadratic (no rows), constraints add one EQ row per (step, joint) after the CartPose
+  // constraint rows (cnt_infos order, JointPosEqConstraint ctor order: step-major); the
+  // tolerance forms have hinge rows (static hinge table below), no abs rows
+  std::vector<int> jpos_row0(THIP_MAX_JPOS, 0), jpos_nrow(THIP_MAX_JPOS, 0);
   for (int k = 0; k < d.n_jpos; ++k)
   {
-    if (!d.jpos_is_cnt[k])
+    if (!d.jpos_is_cnt[k] || P.jpos_ineq[k])
       continue;
-    jpos_slot[static_cast<size_t>(k)] = n_cnts++;
-    if (jpos_ineq[static_cast<size_t>(k)])
-      continue;  // hinge rows (static hinge table below), no abs rows
     jpos_row0[static_cast<size_t>(k)] = static_cast<int>(row_term.size());
-    for (int t = jpos_first[static_cast<size_t>(k)]; t <= jpos_last[static_cast<size_t>(k)]; ++t)
+    for (int t = P.jpos_first[k]; t <= P.jpos_last[k]; ++t)
       for (int j = 0; j < L.D; ++j)
-      {
-        row_term.push_back(k);
-        row_comp.push_back(j);
-        row_step.push_back(t);
-        row_w.push_back(d.jpos_coeffs[k][j]);
-        row_slot.push_back(jpos_slot[static_cast<size_t>(k)]);
-        row_jpos.push_back(1);
-      }
+        add_row(k, j, t, d.jpos_coeffs[k][j], P.jpos_slot[k], 1);
     jpos_nrow[static_cast<size_t>(k)] = static_cast<int>(row_term.size()) - jpos_row0[static_cast<size_t>(k)];
   }
-  for (int x = 0; x < d.n_jvx; ++x)
-    if (d.jvx_is_cnt[x])
-      jvx_slot[static_cast<size_t>(x)] = n_cnts++;
   L.n_abs = static_cast<int>(row_term.size());
   L.n_abs_cost = 0;
   for (int r = 0; r < L.n_abs; ++r)
@@ -510,8 +282,8 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
   // further JointVel tolerance terms: owner n_jpos + 1 + x
   for (int x = 0; x < d.n_jvx; ++x)
   {
-    const int slot = d.jvx_is_cnt[x] ? jvx_slot[static_cast<size_t>(x)] : -1;
-    for (int t = jvx_first[static_cast<size_t>(x)]; t <= jvx_last[static_cast<size_t>(x)] - 1; ++t)
+    const int slot = d.jvx_is_cnt[x] ? P.jvx_slot[x] : -1;
+    for (int t = P.jvx_first[x]; t <= P.jvx_last[x] - 1; ++t)
       for (int j = 0; j < L.D; ++j)
       {
         add_sh(SH_JV_UP, d.n_jpos + 1 + x, j, t, t, slot);
@@ -520,10 +292,10 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
   }
   for (int k = 0; k < d.n_jpos; ++k)
   {
-    if (!jpos_ineq[static_cast<size_t>(k)])
+    if (!P.jpos_ineq[k])
       continue;
-    const int slot = d.jpos_is_cnt[k] ? jpos_slot[static_cast<size_t>(k)] : -1;
-    for (int t = jpos_first[static_cast<size_t>(k)]; t <= jpos_last[static_cast<size_t>(k)]; ++t)
+    const int slot = d.jpos_is_cnt[k] ? P.jpos_slot[k] : -1;
+    for (int t = P.jpos_first[k]; t <= P.jpos_last[k]; ++t)
       for (int j = 0; j < L.D; ++j)
       {
         add_sh(SH_JP_UP, k, j, t, std::min(t, L.N - 2), slot);
@@ -553,32 +325,17 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
   permute(sh_step);
   permute(sh_pair);
   permute(sh_slot);
-  // collision: one cost term per step pair after the CartPose costs
-  // (cost_infos order; CollisionTermInfo::hatch, problem_description.cpp:1747)
-  L.coll = d.coll_enabled ? 1 : 0;
-  L.coll_first = d.coll_first_step;
-  L.coll_last = (d.coll_last_step < 0) ? L.N - 1 : d.coll_last_step;
-  // DISCRETE: one SingleTimestepCollisionEvaluator term per waypoint of [first, last] that is
-  // not a fixed step (problem_description.cpp:1782-1796)
-  L.coll_single = (L.coll && d.coll_continuous == 2) ? 1 : 0;
-  if (L.coll_single)
-    L.coll_last += 1;
+  // collision units and their slots relative to coll_cost0 (-1: a waypoint without a term)
+  L.coll = P.coll;
+  L.coll_first = P.coll_first;
+  L.coll_last = P.coll_last;
+  L.coll_single = P.coll_single;
+  L.coll_cnt = P.coll_cnt;
+  L.coll_cost0 = P.coll_cost0;
+  const int n_units = P.n_units;
   std::vector<int> coll_slot(static_cast<size_t>(L.N), -1);
-  int n_units = 0;
-  for (int t = L.coll_first; L.coll && t < L.coll_last; ++t)
-  {
-    bool fx = false;
-    for (int k = 0; k < d.coll_n_fixed; ++k)
-      fx |= d.coll_fixed_steps[k] == t;
-    if (!(L.coll_single && fx))
-      coll_slot[static_cast<size_t>(t)] = n_units++;
-  }
-  // (constraint form: one ineq constraint term per step pair after the other
-  // constraints, problem_description.cpp:1797-1840 / OptProb eq-then-ineq order)
-  L.coll_cnt = (L.coll && d.coll_is_cnt) ? 1 : 0;
-  L.coll_cost0 = L.coll_cnt ? n_cnts : n_costs;
-  if (L.coll)
-    (L.coll_cnt ? n_cnts : n_costs) += n_units;
+  for (int u = 0; u < n_units; ++u)
+    coll_slot[static_cast<size_t>(P.unit_t[u])] = u;
   if (L.coll)
   {
     // every (sphere, primitive, sub-state) and (self sphere pair, sub-state) candidate of
@@ -599,8 +356,8 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     L.h_cap = 0;
   L.h_cap += n_sh;
   L.hinge = (L.h_cap > 0) ? 1 : 0;
-  L.n_costs = n_costs;
-  L.n_cnts = n_cnts;
+  L.n_costs = P.n_costs;
+  L.n_cnts = P.n_cnts;
   L.nc_base = L.nx + 2 * L.n_abs;
   L.n_rows = L.n_fixed_rows + L.n_abs;
   L.m_base = L.n_rows + L.nc_base;
@@ -940,28 +697,12 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
   const size_t o_xf = push(jvx_first, THIP_MAX_JVX), o_xl = push(jvx_last, THIP_MAX_JVX),
                o_xs = push(jvx_slot, THIP_MAX_JVX);
   // collision model tables: spheres grouped by link, ascending (scan order)
-  std::vector<int> grp_link, grp_s0, grp_ns, sph_order, coll_fixed(static_cast<size_t>(L.N), 0);
-  if (L.coll)
-  {
-    for (int s2 = 0; s2 < d.n_spheres; ++s2)
-      sph_order.push_back(s2);
-    std::stable_sort(sph_order.begin(), sph_order.end(),
-                     [&](int a, int b) { return d.sphere_link[a] < d.sphere_link[b]; });
-    for (size_t k = 0; k < sph_order.size(); ++k)
-    {
-      const int link = d.sphere_link[sph_order[k]];
-      if (grp_link.empty() || grp_link.back() != link)
-      {
-        grp_link.push_back(link);
-        grp_s0.push_back(static_cast<int>(k));
-        grp_ns.push_back(0);
-      }
-      grp_ns.back()++;
-    }
-    for (int k = 0; k < d.coll_n_fixed; ++k)
-      if (d.coll_fixed_steps[k] >= 0 && d.coll_fixed_steps[k] < L.N)
-        coll_fixed[static_cast<size_t>(d.coll_fixed_steps[k])] = 1;
-  }
+  const lowering::SphereGroups sg = L.coll ? lowering::group_spheres_by_link(d) : lowering::SphereGroups();
+  const std::vector<int>& grp_link = sg.grp_link;
+  const std::vector<int>& grp_s0 = sg.grp_s0;
+  const std::vector<int>& grp_ns = sg.grp_ns;
+  const std::vector<int>& sph_order = sg.order;
+  const std::vector<int> coll_fixed(P.coll_fixed, P.coll_fixed + L.N);
   std::vector<int> self_sa, self_sb, self_kp(1, 0);
   if (L.coll)
     self_sphere_pairs(d, self_sa, self_sb, self_kp);

@@ -29,8 +29,8 @@
 #include <vector>
 
 #include "collision_device.hpp"
+#include "desc_lowering.hpp"
 #include "kin_device.hpp"
-#include "self_pairs.hpp"
 
 namespace thip
 {
@@ -455,18 +455,17 @@ int thip_check_create(int device, const thip_problem_desc* desc, const thip_chec
     g_check_create_err = "thip_check_create: " + m;
     return THIP_E_INVALID;
   };
-  if (desc->abi_version != THIP_ABI_VERSION)
-    return reject("descriptor abi_version " + std::to_string(desc->abi_version) + " != THIP_ABI_VERSION " +
-                  std::to_string(THIP_ABI_VERSION));
+  {
+    const std::string why = thip::lowering::abi_mismatch(*desc);
+    if (!why.empty())
+      return reject(why);
+  }
   const thip_chain& ch = desc->chain;
   const int N = desc->n_steps;
-  if (ch.n_dof <= 0 || ch.n_dof > THIP_MAX_DOF || ch.n_links < 1 || ch.n_links > THIP_MAX_LINKS)
-    return reject("chain out of range");
-  for (int k = 1; k < ch.n_links; ++k)
-    if ((ch.joint_type[k] < 0 || ch.joint_type[k] > 3) ||
-        (ch.joint_type[k] != THIP_JOINT_FIXED && (ch.joint_dof[k] < 0 || ch.joint_dof[k] >= ch.n_dof)) ||
-        (ch.is_tree && (ch.parent[k] < 0 || ch.parent[k] >= k)))
-      return reject("bad chain joint / parent table");
+  if (const char* why = thip::lowering::chain_range_finding(ch))
+    return reject(why);
+  if (const char* why = thip::lowering::chain_table_finding(ch))
+    return reject(why);
   if (N < 1 || N > THIP_EVAL_MAX_STEPS)
     return reject("n_steps out of range");
   if (desc->n_prims < 0 || desc->n_prims > THIP_EVAL_MAX_PRIMS)
@@ -514,31 +513,15 @@ int thip_check_create(int device, const thip_problem_desc* desc, const thip_chec
   c->pr.N = N;
   c->pr.n_prims = desc->n_prims;
   thip_chain chain = ch;
-  if (!chain.is_tree)
-    for (int k = 0; k < THIP_MAX_LINKS; ++k)
-      chain.parent[k] = k > 0 ? k - 1 : 0;
+  thip::lowering::fill_serial_parents(chain);
   Model md{};
   {
     const thip_problem_desc& d = *desc;
-    std::vector<int> order;
-    for (int s = 0; s < d.n_spheres; ++s)
-      order.push_back(s);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d.sphere_link[a] < d.sphere_link[b]; });
     md.n_sph = d.n_spheres;
-    for (size_t k = 0; k < order.size(); ++k)
-    {
-      md.sph_order[k] = order[k];
-      const int link = d.sphere_link[order[k]];
-      if (md.n_groups == 0 || md.grp_link[md.n_groups - 1] != link)
-      {
-        md.grp_link[md.n_groups] = link;
-        md.grp_s0[md.n_groups] = static_cast<int>(k);
-        md.grp_ns[md.n_groups] = 0;
-        md.n_groups++;
-      }
-      md.grp_ns[md.n_groups - 1]++;
-      md.slot_grp[k] = md.n_groups - 1;
-    }
+    thip::lowering::store_sphere_groups(thip::lowering::group_spheres_by_link(d), md);
+    for (int g = 0; g < md.n_groups; ++g)
+      for (int k = md.grp_s0[g]; k < md.grp_s0[g] + md.grp_ns[g]; ++k)
+        md.slot_grp[k] = g;
     md.n_self_keys = static_cast<int>(skp.size()) - 1;
     md.n_self_sph = static_cast<int>(ssa.size());
     for (size_t k = 0; k < skp.size(); ++k)
