@@ -10,6 +10,12 @@ not available on this pool and no GPU call is made here).
   target, its own main over csrc/desc_lowering.hpp alone) sweeps out-of-range
   counts and steps through the fused kernel's validator and, where it accepts,
   checks the term plan's invariants.
+* The handles' life cycle: trajopt-1_amd/host/tests/device_handle_san.cpp (same
+  target, its own main, the .hip files' host code compiled in with the
+  sanitizers) takes every <api>_create through its failure path where there is
+  no device (THIP_E_HIP, *out null, the hipSetDevice message, nothing leaked;
+  with a device: created and destroyed) and calls every entry point of every
+  handle with a null handle.
 * The oracle: its known-answer tests (oracle/tests/kat_main.cpp) built with the
   same sanitizers (oracle Makefile target `build/kat_san`).
 """
@@ -67,6 +73,11 @@ def test_front_door_json_fuzz_under_sanitizers(built, seed):
 
 def test_descriptor_lowering_under_sanitizers(built):
     out = _run([str(LIB / "desc_lowering_san")])
+    assert "fail=0" in out
+
+
+def test_device_handles_under_sanitizers(built):
+    out = _run([str(LIB / "device_handle_san")])
     assert "fail=0" in out
 
 

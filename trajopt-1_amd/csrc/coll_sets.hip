@@ -344,10 +344,7 @@ int thip_csets_create(int device, const thip_problem_desc* desc, const thip_cset
     g_csets_create_err = "thip_csets_create: null argument or batch <= 0";
     return THIP_E_INVALID;
   }
-  const Reject reject = [](const std::string& m) {
-    g_csets_create_err = "thip_csets_create: " + m;
-    return THIP_E_INVALID;
-  };
+  const thip::host::CreateError reject{ g_csets_create_err, "thip_csets_create: " };
   if (check_descriptor(*desc, *cfg, reject) != THIP_OK)
     return THIP_E_INVALID;
   // each bound on its own: no sum or difference of caller values before they are known to lie in [0, N)
@@ -365,7 +362,7 @@ int thip_csets_create(int device, const thip_problem_desc* desc, const thip_cset
   if (check_pairs(*desc, cfg->margin, cfg->coeff, reject, ssa, ssb, tab) != THIP_OK)
     return THIP_E_INVALID;
 
-  auto* c = new thip_csets();
+  std::unique_ptr<thip_csets, void (*)(thip_csets*)> c(new thip_csets(), thip_csets_destroy);
   c->pr.margin = cfg->margin;
   c->pr.coeff = cfg->coeff;
   c->pr.buffer = cfg->margin_buffer;
@@ -379,16 +376,11 @@ int thip_csets_create(int device, const thip_problem_desc* desc, const thip_cset
   thip_chain chain;
   std::unique_ptr<Model> md(new Model());
   fill_model(*desc, ssa, ssb, chain, *md);
-  const std::string why = allocate_and_upload(*c, device, batch, *desc, static_cast<size_t>(batch) * n_nodes,
-                                              cfg->max_num_cnt, desc->chain.n_dof, chain, *md, tab);
-  if (!why.empty())
-  {
-    g_csets_create_err = "thip_csets_create: " + why;
-    thip_csets_destroy(c);
+  if (allocate_and_upload(*c, device, batch, *desc, static_cast<size_t>(batch) * n_nodes, cfg->max_num_cnt,
+                          desc->chain.n_dof, chain, *md, tab, reject) != THIP_OK)
     return THIP_E_HIP;
-  }
   c->pr.pmc = c->d_pmc;
-  *out = c;
+  *out = c.release();
   return THIP_OK;
 }
 
@@ -425,7 +417,7 @@ void thip_csets_destroy(thip_csets* cs)
 {
   if (!cs)
     return;
-  release(cs);
+  release(*cs);
   delete cs;
 }
 

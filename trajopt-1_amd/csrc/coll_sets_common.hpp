@@ -1,7 +1,9 @@
 // What the discrete (coll_sets.hip) and the continuous (coll_sets_cont.hip)
 // collision sets share: the robot model, the key packing and the row order, the
-// validation of thip_*_create, and the handle's buffers with their upload, run
-// and free.  Both kernels rest on one invariant: unique keys (check_pairs)
+// validation of thip_*_create, and the handle's buffers with their allocation
+// and fetch; the life cycle itself (stream, events, upload, the start of a run,
+// the timed launch, release) is device_handle.hpp's, as for every handle.  Both
+// kernels rest on one invariant: unique keys (check_pairs)
 // under a strict total order (pack_key, before) and no atomics, so a problem's
 // rows do not depend on its place in the batch and every run gives the same
 // bits.  The kernels' prologue and selection step (compaction, ranking) stay
@@ -14,12 +16,12 @@
 
 #include <algorithm>
 #include <cmath>
-#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "desc_lowering.hpp"
+#include "device_handle.hpp"
 #include "kin_device.hpp"
 
 namespace thip
@@ -72,13 +74,11 @@ __device__ __forceinline__ void sphere_world(const Pose& T, const double* cl, do
 }
 
 // ---------------------------------------------------------------- host side
-using Reject = std::function<int(const std::string&)>;
-
 // thip_*_create's checks of the descriptor and of the config fields both kinds
 // of set have (Cfg: thip_csets_config or thip_ccsets_config).  THIP_OK, or
 // what reject returned for the first finding.
 template <class Cfg>
-inline int check_descriptor(const thip_problem_desc& desc, const Cfg& cfg, const Reject& reject)
+inline int check_descriptor(const thip_problem_desc& desc, const Cfg& cfg, const host::CreateError& reject)
 {
   {
     const std::string why = lowering::abi_mismatch(desc);
@@ -124,7 +124,7 @@ inline int check_descriptor(const thip_problem_desc& desc, const Cfg& cfg, const
 // The checks that follow each file's own (step range, grid, ...): term 0's
 // pair overrides and the self pairs.  Fills the self sphere pairs (ssa, ssb)
 // and tab, term 0's overrides over margin and coeff (pair_data.hpp).
-inline int check_pairs(const thip_problem_desc& desc, double margin, double coeff, const Reject& reject,
+inline int check_pairs(const thip_problem_desc& desc, double margin, double coeff, const host::CreateError& reject,
                        std::vector<int>& ssa, std::vector<int>& ssb, std::vector<double>& tab)
 {
   if (desc.n_coll_pairs < 0 || desc.n_coll_pairs > THIP_MAX_COLL_PAIRS)
@@ -176,30 +176,18 @@ inline void fill_model(const thip_problem_desc& desc, const std::vector<int>& ss
   chain = desc.chain;
   lowering::fill_serial_parents(chain);
   md = Model();
-  md.n_sph = desc.n_spheres;
-  md.n_self_sph = static_cast<int>(ssa.size());
-  for (size_t j = 0; j < ssa.size(); ++j)
-  {
-    md.self_sa[j] = ssa[j];
-    md.self_sb[j] = ssb[j];
-  }
-  for (int s = 0; s < desc.n_spheres; ++s)
-  {
-    md.link[s] = desc.sphere_link[s];
-    md.radius[s] = desc.sphere_radius[s];
-    for (int i = 0; i < 3; ++i)
-      md.center[s][i] = desc.sphere_center[s][i];
-  }
+  lowering::fill_sphere_model(desc, ssa, ssb, md);
+  std::copy(desc.sphere_link, desc.sphere_link + desc.n_spheres, md.link);
   for (int k = 1; k < chain.n_links; ++k)
     md.active[k] = (chain.joint_type[k] != THIP_JOINT_FIXED || md.active[chain.parent[k]]) ? 1 : 0;
 }
 
-// What struct thip_csets and struct thip_ccsets are made of.  items: the
-// launch's workgroups (batch x nodes or segments), rows: items x max_num_cnt,
-// jac_width: D or 2 D.
-struct Handle
+// What struct thip_csets and struct thip_ccsets are made of, over the base every
+// handle has (device_handle.hpp).  items: the launch's workgroups (batch x nodes
+// or segments), rows: items x max_num_cnt, jac_width: D or 2 D.
+struct Handle : host::Handle
 {
-  int device = 0, batch = 0, D = 0, N = 0, n_prims = 0;
+  int D = 0, N = 0, n_prims = 0;
   size_t items = 0, rows = 0, jac_width = 0;
   thip_chain* d_chain = nullptr;
   Model* d_model = nullptr;
@@ -211,30 +199,14 @@ struct Handle
   double* d_coeffs = nullptr;
   int* d_counts = nullptr;
   int* d_keys = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool uploaded = false;
-  double last_ms = -1.0;
-  std::string err;
 };
 
-inline int fail(Handle* h, const std::string& m)
-{
-  h->err = m;
-  return THIP_E_INVALID;
-}
-inline int hipfail(Handle* h, const char* what, hipError_t e)
-{
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return THIP_E_HIP;
-}
-
 // A new handle's sizes, buffers, stream and events; chain, model and pair table
-// uploaded, the scene zeroed.  "" or "<call>: <hip error>"; the caller destroys
-// the handle then.
-inline std::string allocate_and_upload(Handle& h, int device, int batch, const thip_problem_desc& desc, size_t items,
-                                       int R, size_t jac_width, const thip_chain& chain, const Model& md,
-                                       const std::vector<double>& tab)
+// uploaded, the scene zeroed.  THIP_OK, or what bad.hip worded; the handle is
+// released by its owner then.
+inline int allocate_and_upload(Handle& h, int device, int batch, const thip_problem_desc& desc, size_t items, int R,
+                               size_t jac_width, const thip_chain& chain, const Model& md,
+                               const std::vector<double>& tab, const host::CreateError& bad)
 {
   h.device = device;
   h.batch = batch;
@@ -244,75 +216,46 @@ inline std::string allocate_and_upload(Handle& h, int device, int batch, const t
   h.items = items;
   h.rows = items * static_cast<size_t>(R);
   h.jac_width = jac_width;
-  auto bad = [](const char* what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); };
   hipError_t e;
   if ((e = hipSetDevice(h.device)) != hipSuccess)
-    return bad("hipSetDevice", e);
+    return bad.hip("hipSetDevice", e);
   const size_t B = static_cast<size_t>(h.batch), np = static_cast<size_t>(std::max(h.n_prims, 1));
-  if ((e = hipMalloc(&h.d_chain, sizeof(thip_chain))) != hipSuccess ||
-      (e = hipMalloc(&h.d_model, sizeof(Model))) != hipSuccess ||
-      (e = hipMalloc(&h.d_scene, B * np * 16 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&h.d_x, B * static_cast<size_t>(h.N) * h.D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&h.d_values, h.rows * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&h.d_jac, h.rows * h.jac_width * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&h.d_coeffs, h.rows * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&h.d_counts, h.items * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc(&h.d_keys, h.rows * 4 * sizeof(int))) != hipSuccess ||
-      (!tab.empty() && (e = hipMalloc(&h.d_pmc, tab.size() * sizeof(double))) != hipSuccess))
-    return bad("hipMalloc", e);
-  if ((e = hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking)) != hipSuccess)
-    return bad("hipStreamCreate", e);
-  if ((e = hipEventCreate(&h.ev0)) != hipSuccess || (e = hipEventCreate(&h.ev1)) != hipSuccess)
-    return bad("hipEventCreate", e);
+  if ((e = host::alloc(h, h.d_chain, 1)) != hipSuccess || (e = host::alloc(h, h.d_model, 1)) != hipSuccess ||
+      (e = host::alloc(h, h.d_scene, B * np * 16)) != hipSuccess ||
+      (e = host::alloc(h, h.d_x, B * static_cast<size_t>(h.N) * h.D)) != hipSuccess ||
+      (e = host::alloc(h, h.d_values, h.rows)) != hipSuccess ||
+      (e = host::alloc(h, h.d_jac, h.rows * h.jac_width)) != hipSuccess ||
+      (e = host::alloc(h, h.d_coeffs, h.rows)) != hipSuccess || (e = host::alloc(h, h.d_counts, h.items)) != hipSuccess ||
+      (e = host::alloc(h, h.d_keys, h.rows * 4)) != hipSuccess ||
+      (!tab.empty() && (e = host::alloc(h, h.d_pmc, tab.size())) != hipSuccess))
+    return bad.hip("hipMalloc", e);
+  if ((e = host::open_stream(h)) != hipSuccess)
+    return bad.hip("hipStreamCreate", e);
+  if ((e = host::open_events(h)) != hipSuccess)
+    return bad.hip("hipEventCreate", e);
   if ((e = hipMemcpyAsync(h.d_chain, &chain, sizeof(thip_chain), hipMemcpyHostToDevice, h.stream)) != hipSuccess ||
       (e = hipMemcpyAsync(h.d_model, &md, sizeof(Model), hipMemcpyHostToDevice, h.stream)) != hipSuccess ||
       (!tab.empty() && (e = hipMemcpyAsync(h.d_pmc, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice,
                                            h.stream)) != hipSuccess) ||
       (e = hipMemsetAsync(h.d_scene, 0, B * np * 16 * sizeof(double), h.stream)) != hipSuccess ||
       (e = hipStreamSynchronize(h.stream)) != hipSuccess)
-    return bad("hipMemcpy", e);
-  return "";
+    return bad.hip("hipMemcpy", e);
+  return THIP_OK;
 }
 
 // thip_*_upload / thip_*_upload_device (`who`)
 inline int upload_scene(Handle* h, const double* scene, hipMemcpyKind kind, const char* who)
 {
-  if (!h)
-    return THIP_E_INVALID;
-  if (h->n_prims > 0 && !scene)
-    return fail(h, std::string(who) + ": scene required when n_prims > 0");
-  hipError_t e;
-  if ((e = hipSetDevice(h->device)) != hipSuccess)
-    return hipfail(h, "hipSetDevice", e);
-  if (h->n_prims > 0 &&
-      ((e = hipMemcpyAsync(h->d_scene, scene,
-                           static_cast<size_t>(h->batch) * static_cast<size_t>(h->n_prims) * 16 * sizeof(double), kind,
-                           h->stream)) != hipSuccess ||
-       (e = hipStreamSynchronize(h->stream)) != hipSuccess))
-    return hipfail(h, "hipMemcpy(scene)", e);
-  h->uploaded = true;
-  return THIP_OK;
+  return h ? host::upload_scene(h, h->d_scene, h->n_prims, scene, kind, who) : THIP_E_INVALID;
 }
 
-// The start of <api>_run (x on the host: staged in d_x) and of <api>_run_device;
-// api: "thip_csets" or "thip_ccsets".  d_x: where the kernel reads.
+// The start of <api>_run and of <api>_run_device; api: "thip_csets" or "thip_ccsets"
 inline int stage_x(Handle* h, const char* api, const double* x, bool on_host, const double*& d_x)
 {
   if (!h)
     return THIP_E_INVALID;
-  const std::string who = std::string(api) + (on_host ? "_run" : "_run_device");
-  if (!x)
-    return fail(h, who + (on_host ? ": null x" : ": null d_x"));
-  if (!h->uploaded)
-    return fail(h, who + ": " + api + "_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(h->device)) != hipSuccess)
-    return hipfail(h, "hipSetDevice", e);
-  if (on_host && (e = hipMemcpyAsync(h->d_x, x, static_cast<size_t>(h->batch) * static_cast<size_t>(h->N) * h->D *
-                                                    sizeof(double), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-    return hipfail(h, "hipMemcpy(x)", e);
-  d_x = on_host ? h->d_x : x;
-  return THIP_OK;
+  return host::stage_x(h, api, on_host, x, true, "", h->d_x,
+                       static_cast<size_t>(h->batch) * static_cast<size_t>(h->N) * h->D, d_x);
 }
 
 // launch() between the two events, then the results to the host (a null
@@ -321,51 +264,20 @@ template <class Launch>
 inline int launch_and_fetch(Handle* h, const char* kernel, Launch launch, double* values, double* jac, double* coeffs,
                             int* counts, int* keys)
 {
-  hipError_t e;
-  if ((e = hipEventRecord(h->ev0, h->stream)) != hipSuccess)
-    return hipfail(h, "hipEventRecord", e);
-  launch();
-  if ((e = hipGetLastError()) != hipSuccess)
-    return hipfail(h, (std::string(kernel) + " launch").c_str(), e);
-  if ((e = hipEventRecord(h->ev1, h->stream)) != hipSuccess)
-    return hipfail(h, "hipEventRecord", e);
-  auto back = [&](void* dst, const void* src, size_t bytes) {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+  auto run = [&] {
+    launch();
+    return host::launched(h, kernel);
   };
-  if ((e = back(values, h->d_values, h->rows * sizeof(double))) != hipSuccess ||
-      (e = back(jac, h->d_jac, h->rows * h->jac_width * sizeof(double))) != hipSuccess ||
-      (e = back(coeffs, h->d_coeffs, h->rows * sizeof(double))) != hipSuccess ||
-      (e = back(counts, h->d_counts, h->items * sizeof(int))) != hipSuccess ||
-      (e = back(keys, h->d_keys, h->rows * 4 * sizeof(int))) != hipSuccess ||
-      (e = hipStreamSynchronize(h->stream)) != hipSuccess)
-    return hipfail(h, kernel, e);
-  float ms = -1.0f;
-  h->last_ms = hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess ? static_cast<double>(ms) : -1.0;
-  return THIP_OK;
-}
-
-// Drains the stream and frees what Handle holds; the caller deletes the object.
-inline void release(Handle* h)
-{
-  hipSetDevice(h->device);
-  if (h->stream)
-    hipStreamSynchronize(h->stream);
-  hipFree(h->d_chain);
-  hipFree(h->d_model);
-  hipFree(h->d_pmc);
-  hipFree(h->d_scene);
-  hipFree(h->d_x);
-  hipFree(h->d_values);
-  hipFree(h->d_jac);
-  hipFree(h->d_coeffs);
-  hipFree(h->d_counts);
-  hipFree(h->d_keys);
-  if (h->ev0)
-    hipEventDestroy(h->ev0);
-  if (h->ev1)
-    hipEventDestroy(h->ev1);
-  if (h->stream)
-    hipStreamDestroy(h->stream);
+  auto fetch = [&] {
+    hipError_t e;
+    if ((e = host::to_host(h, values, h->d_values, h->rows * sizeof(double))) != hipSuccess ||
+        (e = host::to_host(h, jac, h->d_jac, h->rows * h->jac_width * sizeof(double))) != hipSuccess ||
+        (e = host::to_host(h, coeffs, h->d_coeffs, h->rows * sizeof(double))) != hipSuccess ||
+        (e = host::to_host(h, counts, h->d_counts, h->items * sizeof(int))) != hipSuccess)
+      return e;
+    return host::to_host(h, keys, h->d_keys, h->rows * 4 * sizeof(int));
+  };
+  return host::timed_run(h, kernel, run, fetch);
 }
 }  // namespace sets
 }  // namespace thip

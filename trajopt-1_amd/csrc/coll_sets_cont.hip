@@ -605,10 +605,7 @@ int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccs
     g_ccsets_create_err = "thip_ccsets_create: null argument or batch <= 0";
     return THIP_E_INVALID;
   }
-  const Reject reject = [](const std::string& m) {
-    g_ccsets_create_err = "thip_ccsets_create: " + m;
-    return THIP_E_INVALID;
-  };
+  const thip::host::CreateError reject{ g_ccsets_create_err, "thip_ccsets_create: " };
   if (check_descriptor(*desc, *cfg, reject) != THIP_OK)
     return THIP_E_INVALID;
   const int et = cfg->evaluator_type;
@@ -640,7 +637,7 @@ int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccs
   if (check_pairs(*desc, cfg->margin, cfg->coeff, reject, ssa, ssb, tab) != THIP_OK)
     return THIP_E_INVALID;
 
-  auto* c = new thip_ccsets();
+  std::unique_ptr<thip_ccsets, void (*)(thip_ccsets*)> c(new thip_ccsets(), thip_ccsets_destroy);
   c->pr.margin = cfg->margin;
   c->pr.coeff = cfg->coeff;
   c->pr.buffer = cfg->margin_buffer;
@@ -662,23 +659,17 @@ int thip_ccsets_create(int device, const thip_problem_desc* desc, const thip_ccs
   for (int k = 0; seg_fixed && k < n_seg; ++k)
     fixed[k] = seg_fixed[k];
 
-  auto hfail = [&](const std::string& why) {
-    g_ccsets_create_err = "thip_ccsets_create: " + why;
-    thip_ccsets_destroy(c);
+  if (allocate_and_upload(*c, device, batch, *desc, static_cast<size_t>(batch) * n_seg, cfg->max_num_cnt,
+                          2 * desc->chain.n_dof, chain, *md, tab, reject) != THIP_OK)
     return THIP_E_HIP;
-  };
-  const std::string why = allocate_and_upload(*c, device, batch, *desc, static_cast<size_t>(batch) * n_seg,
-                                              cfg->max_num_cnt, 2 * desc->chain.n_dof, chain, *md, tab);
-  if (!why.empty())
-    return hfail(why);
   hipError_t e;
-  if ((e = hipMalloc(&c->d_fixed, fixed.size() * sizeof(int))) != hipSuccess)
-    return hfail(std::string("hipMalloc: ") + hipGetErrorString(e));
+  if ((e = alloc(*c, c->d_fixed, fixed.size())) != hipSuccess)
+    return reject.hip("hipMalloc", e);
   if ((e = hipMemcpy(c->d_fixed, fixed.data(), fixed.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
-    return hfail(std::string("hipMemcpy: ") + hipGetErrorString(e));
+    return reject.hip("hipMemcpy", e);
   c->pr.pmc = c->d_pmc;
   c->pr.seg_fixed = c->d_fixed;
-  *out = c;
+  *out = c.release();
   return THIP_OK;
 }
 
@@ -715,8 +706,7 @@ void thip_ccsets_destroy(thip_ccsets* cs)
 {
   if (!cs)
     return;
-  release(cs);
-  hipFree(cs->d_fixed);
+  release(*cs);
   delete cs;
 }
 

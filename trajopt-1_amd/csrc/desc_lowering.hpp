@@ -76,6 +76,25 @@ inline void store_sphere_groups(const SphereGroups& g, DeviceModel& m)
   std::copy(g.order.begin(), g.order.end(), m.sph_order);
 }
 
+// What the device models of the robot's spheres share: n_sph, center, radius
+// and the self-collision sphere pairs (ssa, ssb: self_sphere_pairs).  A model's
+// own fields (link, where it has one) stay with its create.
+template <class DeviceModel>
+inline void fill_sphere_model(const thip_problem_desc& d, const std::vector<int>& ssa, const std::vector<int>& ssb,
+                              DeviceModel& m)
+{
+  m.n_sph = d.n_spheres;
+  m.n_self_sph = static_cast<int>(ssa.size());
+  std::copy(ssa.begin(), ssa.end(), m.self_sa);
+  std::copy(ssb.begin(), ssb.end(), m.self_sb);
+  for (int s = 0; s < d.n_spheres; ++s)
+  {
+    m.radius[s] = d.sphere_radius[s];
+    for (int i = 0; i < 3; ++i)
+      m.center[s][i] = d.sphere_center[s][i];
+  }
+}
+
 // "" or the generic evaluators' sentence for a descriptor of another header
 inline std::string abi_mismatch(const thip_problem_desc& d)
 {

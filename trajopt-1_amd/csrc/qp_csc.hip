@@ -39,12 +39,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
+#include <memory>
 #include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/trajopt_hip.h"
+#include "device_handle.hpp"
 #include "kkt_symbolic.hpp"
 
 namespace thip_qp_dev
@@ -1613,12 +1615,11 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
 
 using namespace thip_qp_dev;
 
-struct thip_qp
+struct thip_qp : thip::host::Handle  // stream: thip_qp_submit / thip_qp_collect; no events
 {
-  int device = 0, batch = 0, n = 0, m = 0, nnz_p = 0, nnz_a = 0;
+  int n = 0, m = 0, nnz_p = 0, nnz_a = 0;
   long long nnz_l = 0;  // entries of the KKT factor L (thip_qp_factor_nnz)
   int max_level = 0;    // nodes of the widest elimination-tree level (thip_qp_shape)
-  hipStream_t stream = nullptr;  // thip_qp_submit / thip_qp_collect
   int pending = 0;               // QPs submitted and not yet collected
   bool staged = false;           // thip_qp_stage: inputs on the device, launch deferred
   QpArgs staged_args{};
@@ -1637,7 +1638,6 @@ struct thip_qp
   thip_qp_info* d_info = nullptr;
   long long in_doubles = 0;
   size_t lds = 0;
-  std::string err;
   // resident workspace (thip_qp_setup ...): the settings of its setup
   thip_osqp_settings rs{};
   bool resident = false;
@@ -1650,6 +1650,8 @@ extern "C" {
 int thip_qp_create(int device, int n, int m, const int* P_colptr, const int* P_rowind, const int* A_colptr,
                    const int* A_rowind, int batch, thip_qp** out)
 {
+  if (out)
+    *out = nullptr;
   if (!out || n <= 0 || m < 0 || batch <= 0 || !P_colptr || !A_colptr)
   {
     g_qp_create_err = "thip_qp_create: bad arguments";
@@ -1694,7 +1696,7 @@ int thip_qp_create(int device, int n, int m, const int* P_colptr, const int* P_r
     g_qp_create_err = "thip_qp_create: " + why;
     return THIP_E_INVALID;
   }
-  auto* q = new thip_qp();
+  std::unique_ptr<thip_qp, void (*)(thip_qp*)> q(new thip_qp(), thip_qp_destroy);
   q->device = device;
   q->batch = batch;
   q->n = n;
@@ -1827,25 +1829,20 @@ int thip_qp_create(int device, int n, int m, const int* P_colptr, const int* P_r
       q->lds = static_cast<size_t>(o);
     }
   }
-  auto fail = [&](const std::string& msg) {
-    g_qp_create_err = msg;
-    thip_qp_destroy(q);
-    return THIP_E_HIP;
-  };
+  const thip::host::CreateError bad{ g_qp_create_err, "thip_qp_create: " };
   hipError_t e;
   if ((e = hipSetDevice(device)) != hipSuccess)
-    return fail(std::string("hipSetDevice: ") + hipGetErrorString(e));
-  if ((e = hipMalloc(&q->d_idx, idx.size() * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc(&q->d_ws, static_cast<size_t>(q->pat.stride) * batch * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&q->d_in, static_cast<size_t>(q->in_doubles + 2LL * n + m + 2) * batch * sizeof(double))) !=
-          hipSuccess ||
-      (e = hipMalloc(&q->d_out, static_cast<size_t>(n + m) * batch * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&q->d_info, sizeof(thip_qp_info) * batch)) != hipSuccess)
-    return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
+    return bad.hip("hipSetDevice", e);
+  if ((e = alloc(*q, q->d_idx, idx.size())) != hipSuccess ||
+      (e = alloc(*q, q->d_ws, static_cast<size_t>(q->pat.stride) * batch)) != hipSuccess ||
+      (e = alloc(*q, q->d_in, static_cast<size_t>(q->in_doubles + 2LL * n + m + 2) * batch)) != hipSuccess ||
+      (e = alloc(*q, q->d_out, static_cast<size_t>(n + m) * batch)) != hipSuccess ||
+      (e = alloc(*q, q->d_info, static_cast<size_t>(batch))) != hipSuccess)
+    return bad.hip("hipMalloc", e);
   if ((e = hipMemcpy(q->d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(std::string("hipMemcpy: ") + hipGetErrorString(e));
-  if ((e = hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking)) != hipSuccess)
-    return fail(std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    return bad.hip("hipMemcpy", e);
+  if ((e = open_stream(*q)) != hipSuccess)
+    return bad.hip("hipStreamCreate", e);
   q->pat.Pp = q->d_idx + oPp;
   q->pat.Pi = q->d_idx + oPi;
   q->pat.Prp = q->d_idx + oPrp;
@@ -1873,7 +1870,7 @@ int thip_qp_create(int device, int n, int m, const int* P_colptr, const int* P_r
   q->pat.fwk = q->d_idx + oFwk;
   q->pat.fwa = q->d_idx + oFwa;
   q->pat.fwb = q->d_idx + oFwb;
-  *out = q;
+  *out = q.release();
   return THIP_OK;
 }
 
@@ -2052,12 +2049,9 @@ int thip_qp_launch_staged(thip_qp* const* qps, int n)
   lead->h_first[static_cast<size_t>(n)] = total;
   if (lead->list_cap < n)
   {
-    hipFree(lead->d_list);
-    hipFree(lead->d_first);
-    lead->d_list = nullptr;
-    lead->d_first = nullptr;
-    if ((e = hipMalloc(&lead->d_list, sizeof(QpArgs) * n)) != hipSuccess ||
-        (e = hipMalloc(&lead->d_first, sizeof(int) * (n + 1))) != hipSuccess)
+    drop(*lead, lead->d_first);
+    if ((e = regrow(*lead, lead->d_list, static_cast<size_t>(n))) != hipSuccess ||
+        (e = regrow(*lead, lead->d_first, static_cast<size_t>(n) + 1)) != hipSuccess)
     {
       lead->list_cap = 0;
       return fail(THIP_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -2372,24 +2366,12 @@ void thip_qp_destroy(thip_qp* q)
 {
   if (!q)
     return;
-  hipSetDevice(q->device);
   // an uncollected group launch runs on another object's stream (done_stream,
   // which may already be destroyed) and may still read this object's buffers:
   // wait for the whole device then
-  if (q->pending)
+  if (q->pending && hipSetDevice(q->device) == hipSuccess)
     hipDeviceSynchronize();
-  if (q->stream)
-  {
-    hipStreamSynchronize(q->stream);
-    hipStreamDestroy(q->stream);
-  }
-  hipFree(q->d_list);
-  hipFree(q->d_first);
-  hipFree(q->d_idx);
-  hipFree(q->d_ws);
-  hipFree(q->d_in);
-  hipFree(q->d_out);
-  hipFree(q->d_info);
+  release(*q);
   delete q;
 }
 

@@ -37,11 +37,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "collision_device.hpp"
 #include "desc_lowering.hpp"
+#include "device_handle.hpp"
 #include "kin_device.hpp"
 
 namespace thip
@@ -820,9 +822,8 @@ __global__ __launch_bounds__(kCvChunk) void cart_vel_kernel(const thip_chain* ch
 
 using namespace thip::ev;
 
-struct thip_eval
+struct thip_eval : thip::host::Handle  // no events: nothing here is timed
 {
-  int device = 0, batch = 0;
   thip_problem_desc desc{};
   thip_chain* d_chain = nullptr;
   Spheres* d_sph = nullptr;
@@ -848,28 +849,13 @@ struct thip_eval
   // per collision term: its unit table (offset into d_units) and kernel parameters
   std::vector<int> unit_off, unit_n;
   std::vector<CollTerm> terms;
-  std::vector<double*> d_pair;  // per term: its pair table (pair_data.hpp) or null
   int max_units = 0;
-  hipStream_t stream = nullptr;
-  bool uploaded = false;
-  std::string err;
 };
 
 static thread_local std::string g_eval_create_err;
 
 namespace
 {
-int fail(thip_eval* ev, const std::string& m)
-{
-  ev->err = m;
-  return THIP_E_INVALID;
-}
-int hipfail(thip_eval* ev, const char* what, hipError_t e)
-{
-  ev->err = std::string(what) + ": " + hipGetErrorString(e);
-  return THIP_E_HIP;
-}
-
 // the units of a collision term: free waypoints of [first, last] (DISCRETE) or step
 // pairs (problem_description.cpp:1735-1858)
 bool term_units(int N, int first, int last, int n_fixed, const int* fixed_steps, int cont, std::vector<Unit>& out,
@@ -907,15 +893,14 @@ extern "C" {
 
 int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_eval** out)
 {
+  if (out)
+    *out = nullptr;
   if (!desc || !out || batch <= 0)
   {
     g_eval_create_err = "thip_eval_create: null argument or batch <= 0";
     return THIP_E_INVALID;
   }
-  auto reject = [](const std::string& m) {
-    g_eval_create_err = "thip_eval_create: " + m;
-    return THIP_E_INVALID;
-  };
+  const thip::host::CreateError reject{ g_eval_create_err, "thip_eval_create: " };
   {
     const std::string why = thip::lowering::abi_mismatch(*desc);
     if (!why.empty())
@@ -974,7 +959,7 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
     if (desc->sphere_link[s] < 1 || desc->sphere_link[s] >= ch.n_links || !(desc->sphere_radius[s] >= 0))
       return reject("collision: bad robot sphere");
 
-  auto* ev = new thip_eval();
+  std::unique_ptr<thip_eval, void (*)(thip_eval*)> ev(new thip_eval(), thip_eval_destroy);
   ev->device = device;
   ev->batch = batch;
   ev->desc = *desc;
@@ -999,18 +984,12 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
     tm.contact_test = main ? d.coll_contact_test : x->contact_test;
     const int nf = main ? d.coll_n_fixed : x->n_fixed;
     if (cont < 0 || cont > 2 || nf < 0 || nf > THIP_MAX_STEPS || (!tm.single && !(tm.lvs > 0)) || !(tm.buffer >= 0))
-    {
-      delete ev;
       return reject("collision term " + std::to_string(k) + ": bad evaluator / lvs / buffer / fixed steps");
-    }
     std::string why;
     ev->unit_off.push_back(static_cast<int>(units.size()));
     if (!term_units(N, main ? d.coll_first_step : x->first_step, main ? d.coll_last_step : x->last_step, nf,
                     main ? d.coll_fixed_steps : x->fixed_steps, cont, units, why))
-    {
-      delete ev;
       return reject(why);
-    }
     ev->unit_n.push_back(static_cast<int>(units.size()) - ev->unit_off.back());
     ev->max_units = std::max(ev->max_units, ev->unit_n.back());
     ev->terms.push_back(tm);
@@ -1022,10 +1001,7 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
     std::vector<int> ssa, ssb, skp;
     const std::string why = thip::self_sphere_pairs(d, ssa, ssb, skp);
     if (!why.empty())
-    {
-      delete ev;
       return reject(why);
-    }
     sp.n_self_keys = static_cast<int>(skp.size()) - 1;
     sp.n_self_sph = static_cast<int>(ssa.size());
     for (size_t k = 0; k < ssa.size(); ++k)
@@ -1043,29 +1019,20 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
         sp.center[s][i] = d.sphere_center[s][i];
     }
   }
-  auto hfail = [&](const char* what, hipError_t e) {
-    g_eval_create_err = std::string("thip_eval_create: ") + what + ": " + hipGetErrorString(e);
-    thip_eval_destroy(ev);
-    return THIP_E_HIP;
-  };
   hipError_t e;
   if ((e = hipSetDevice(device)) != hipSuccess)
-    return hfail("hipSetDevice", e);
+    return reject.hip("hipSetDevice", e);
   const size_t B = static_cast<size_t>(batch), D = static_cast<size_t>(d.chain.n_dof);
   const size_t nc = static_cast<size_t>(std::max(d.n_cart, 1)), np = static_cast<size_t>(std::max(d.n_prims, 1));
-  if ((e = hipMalloc(&ev->d_chain, sizeof(thip_chain))) != hipSuccess ||
-      (e = hipMalloc(&ev->d_sph, sizeof(Spheres))) != hipSuccess ||
-      (e = hipMalloc(&ev->d_tgt, B * nc * 12 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ev->d_scene, B * np * 16 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ev->d_x, B * static_cast<size_t>(N) * D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ev->d_err, B * 6 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ev->d_jac, B * 6 * D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ev->d_counts, (B * static_cast<size_t>(std::max(ev->max_units, 1)) + B) * sizeof(int))) !=
-          hipSuccess ||
-      (e = hipMalloc(&ev->d_units, std::max<size_t>(units.size(), 1) * sizeof(Unit))) != hipSuccess)
-    return hfail("hipMalloc", e);
-  if ((e = hipStreamCreateWithFlags(&ev->stream, hipStreamNonBlocking)) != hipSuccess)
-    return hfail("hipStreamCreate", e);
+  if ((e = alloc(*ev, ev->d_chain, 1)) != hipSuccess || (e = alloc(*ev, ev->d_sph, 1)) != hipSuccess ||
+      (e = alloc(*ev, ev->d_tgt, B * nc * 12)) != hipSuccess || (e = alloc(*ev, ev->d_scene, B * np * 16)) != hipSuccess ||
+      (e = alloc(*ev, ev->d_x, B * static_cast<size_t>(N) * D)) != hipSuccess ||
+      (e = alloc(*ev, ev->d_err, B * 6)) != hipSuccess || (e = alloc(*ev, ev->d_jac, B * 6 * D)) != hipSuccess ||
+      (e = alloc(*ev, ev->d_counts, B * static_cast<size_t>(std::max(ev->max_units, 1)) + B)) != hipSuccess ||
+      (e = alloc(*ev, ev->d_units, std::max<size_t>(units.size(), 1))) != hipSuccess)
+    return reject.hip("hipMalloc", e);
+  if ((e = open_stream(*ev)) != hipSuccess)
+    return reject.hip("hipStreamCreate", e);
   if ((e = hipMemcpyAsync(ev->d_chain, &d.chain, sizeof(thip_chain), hipMemcpyHostToDevice, ev->stream)) !=
           hipSuccess ||
       (e = hipMemcpyAsync(ev->d_sph, &sp, sizeof(Spheres), hipMemcpyHostToDevice, ev->stream)) != hipSuccess ||
@@ -1074,7 +1041,7 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
       (e = hipMemsetAsync(ev->d_tgt, 0, B * nc * 12 * sizeof(double), ev->stream)) != hipSuccess ||
       (e = hipMemsetAsync(ev->d_scene, 0, B * np * 16 * sizeof(double), ev->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(ev->stream)) != hipSuccess)
-    return hfail("hipMemcpy", e);
+    return reject.hip("hipMemcpy", e);
   // every CartPose term's arguments and waypoint (cart_eval_all_kernel)
   if (d.n_cart > 0)
   {
@@ -1087,15 +1054,15 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
       if (d.cart_step[k] < 0 || d.cart_step[k] >= N)
         return reject("CartPose term waypoint out of range");
     }
-    if ((e = hipMalloc(&ev->d_cargs, cargs.size() * sizeof(CartArgs))) != hipSuccess ||
-        (e = hipMalloc(&ev->d_csteps, steps.size() * sizeof(int))) != hipSuccess ||
-        (e = hipMalloc(&ev->d_err_all, B * nc * 6 * sizeof(double))) != hipSuccess ||
-        (e = hipMalloc(&ev->d_jac_all, B * nc * 6 * D * sizeof(double))) != hipSuccess)
-      return hfail("hipMalloc(CartPose terms)", e);
+    if ((e = alloc(*ev, ev->d_cargs, cargs.size())) != hipSuccess ||
+        (e = alloc(*ev, ev->d_csteps, steps.size())) != hipSuccess ||
+        (e = alloc(*ev, ev->d_err_all, B * nc * 6)) != hipSuccess ||
+        (e = alloc(*ev, ev->d_jac_all, B * nc * 6 * D)) != hipSuccess)
+      return reject.hip("hipMalloc(CartPose terms)", e);
     if ((e = hipMemcpy(ev->d_cargs, cargs.data(), cargs.size() * sizeof(CartArgs), hipMemcpyHostToDevice)) !=
             hipSuccess ||
         (e = hipMemcpy(ev->d_csteps, steps.data(), steps.size() * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess)
-      return hfail("hipMemcpy(CartPose terms)", e);
+      return reject.hip("hipMemcpy(CartPose terms)", e);
   }
   // every CartVel term's arguments and the pair count (cart_vel_kernel)
   if (d.n_cvel > 0)
@@ -1108,12 +1075,11 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
       ev->cv_pairs += d.cvel_last_step[k] - d.cvel_first_step[k] + 1;
     }
     const size_t P = static_cast<size_t>(ev->cv_pairs);
-    if ((e = hipMalloc(&ev->d_cvterms, cv.size() * sizeof(CvelTerm))) != hipSuccess ||
-        (e = hipMalloc(&ev->d_cv_err, B * P * 6 * sizeof(double))) != hipSuccess ||
-        (e = hipMalloc(&ev->d_cv_jac, B * P * 12 * D * sizeof(double))) != hipSuccess)
-      return hfail("hipMalloc(CartVel terms)", e);
+    if ((e = alloc(*ev, ev->d_cvterms, cv.size())) != hipSuccess || (e = alloc(*ev, ev->d_cv_err, B * P * 6)) != hipSuccess ||
+        (e = alloc(*ev, ev->d_cv_jac, B * P * 12 * D)) != hipSuccess)
+      return reject.hip("hipMalloc(CartVel terms)", e);
     if ((e = hipMemcpy(ev->d_cvterms, cv.data(), cv.size() * sizeof(CvelTerm), hipMemcpyHostToDevice)) != hipSuccess)
-      return hfail("hipMemcpy(CartVel terms)", e);
+      return reject.hip("hipMemcpy(CartVel terms)", e);
   }
   // per link-pair margins of each collision term (coefficients are the host's)
   for (size_t k = 0; k < ev->terms.size(); ++k)
@@ -1122,15 +1088,14 @@ int thip_eval_create(int device, const thip_problem_desc* desc, int batch, thip_
     double* dp = nullptr;
     if (thip::coll_pair_table(d, static_cast<int>(k), tab))
     {
-      if ((e = hipMalloc(&dp, tab.size() * sizeof(double))) != hipSuccess)
-        return hfail("hipMalloc(pair table)", e);
-      ev->d_pair.push_back(dp);
+      if ((e = alloc(*ev, dp, tab.size())) != hipSuccess)
+        return reject.hip("hipMalloc(pair table)", e);
       if ((e = hipMemcpy(dp, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess)
-        return hfail("hipMemcpy(pair table)", e);
+        return reject.hip("hipMemcpy(pair table)", e);
       ev->terms[k].pmc = dp;
     }
   }
-  *out = ev;
+  *out = ev.release();
   return THIP_OK;
 }
 
@@ -1289,9 +1254,7 @@ int thip_eval_collision(thip_eval* ev, int term, const double* x, double* record
     const size_t need = B * static_cast<size_t>(nu) * ev->ucap * W;
     if (need > ev->stage_doubles)
     {
-      hipFree(ev->d_stage);
-      ev->d_stage = nullptr;
-      if ((e = hipMalloc(&ev->d_stage, need * sizeof(double))) != hipSuccess)
+      if ((e = regrow(*ev, ev->d_stage, need)) != hipSuccess)
         return hipfail(ev, "hipMalloc(contact records)", e);
       ev->stage_doubles = need;
     }
@@ -1313,9 +1276,7 @@ int thip_eval_collision(thip_eval* ev, int term, const double* x, double* record
   const size_t need_out = B * static_cast<size_t>(std::max(cap, 1)) * W;
   if (need_out > ev->out_doubles)
   {
-    hipFree(ev->d_out);
-    ev->d_out = nullptr;
-    if ((e = hipMalloc(&ev->d_out, need_out * sizeof(double))) != hipSuccess)
+    if ((e = regrow(*ev, ev->d_out, need_out)) != hipSuccess)
       return hipfail(ev, "hipMalloc(records)", e);
     ev->out_doubles = need_out;
   }
@@ -1335,31 +1296,7 @@ void thip_eval_destroy(thip_eval* ev)
 {
   if (!ev)
     return;
-  hipSetDevice(ev->device);
-  if (ev->stream)
-    hipStreamSynchronize(ev->stream);
-  hipFree(ev->d_chain);
-  hipFree(ev->d_sph);
-  hipFree(ev->d_tgt);
-  hipFree(ev->d_scene);
-  hipFree(ev->d_x);
-  hipFree(ev->d_err);
-  hipFree(ev->d_jac);
-  hipFree(ev->d_cargs);
-  hipFree(ev->d_csteps);
-  hipFree(ev->d_err_all);
-  hipFree(ev->d_jac_all);
-  hipFree(ev->d_cvterms);
-  hipFree(ev->d_cv_err);
-  hipFree(ev->d_cv_jac);
-  hipFree(ev->d_stage);
-  hipFree(ev->d_out);
-  hipFree(ev->d_counts);
-  hipFree(ev->d_units);
-  for (double* dp : ev->d_pair)
-    hipFree(dp);
-  if (ev->stream)
-    hipStreamDestroy(ev->stream);
+  release(*ev);
   delete ev;
 }
 

@@ -32,11 +32,13 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "collision_device.hpp"
 #include "desc_lowering.hpp"
+#include "device_handle.hpp"
 #include "kin_device.hpp"
 #include "layout.hpp"
 
@@ -460,9 +462,8 @@ __global__ __launch_bounds__(kTvBlock) void coll_reduce_kernel(const Model* mode
 using namespace thip;
 using namespace thip::tv;
 
-struct thip_terms
+struct thip_terms : thip::host::Handle
 {
-  int device = 0, batch = 0;
   thip_problem_desc desc{};
   Slots slots{};
   std::vector<thip_term_slot> table;
@@ -484,11 +485,6 @@ struct thip_terms
   double* d_rec = nullptr;
   int* d_cnt = nullptr;
   int rec_cap = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool uploaded = false;
-  double last_ms = -1.0;
-  std::string err;
 };
 
 static thread_local std::string g_terms_create_err;
@@ -562,28 +558,16 @@ void fill_slots(const thip_problem_desc& d, const lowering::TermPlan& P, Slots& 
   copy_array(S.coll_fixed, P.coll_fixed);
 }
 
-int tfail(thip_terms* t, const std::string& m)
-{
-  t->err = m;
-  return THIP_E_INVALID;
-}
-int thipfail(thip_terms* t, const char* what, hipError_t e)
-{
-  t->err = std::string(what) + ": " + hipGetErrorString(e);
-  return THIP_E_HIP;
-}
-
-int run_on_device(thip_terms* t, const double* d_x, double* costs, double* viols)
+// the kernels of a run, in stream order
+int launch_kernels(thip_terms* t, const double* d_x)
 {
   const size_t B = static_cast<size_t>(t->batch);
   const Slots& S = t->slots;
   hipError_t e;
-  if ((e = hipEventRecord(t->ev0, t->stream)) != hipSuccess)
-    return thipfail(t, "hipEventRecord", e);
   hipLaunchKernelGGL(term_values_kernel, dim3(t->batch), dim3(kTvBlock), 0, t->stream, t->d_desc, t->d_slots, t->batch,
                      d_x, t->d_tgt, t->d_jpt, t->d_costs, t->d_viols);
-  if ((e = hipGetLastError()) != hipSuccess)
-    return thipfail(t, "term_values_kernel launch", e);
+  if (const int rc = launched(t, "term_values_kernel"); rc != THIP_OK)
+    return rc;
   if (S.coll && S.n_units > 0 && t->ev)
   {
     // FIRST / CLOSEST: coll_eval_kernel's records of every problem, then their per-unit sums
@@ -593,18 +577,17 @@ int run_on_device(thip_terms* t, const double* d_x, double* costs, double* viols
     t->h_cnt.assign(B, 0);
     if ((e = hipMemcpyAsync(t->h_x.data(), d_x, nx * sizeof(double), hipMemcpyDeviceToHost, t->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(t->stream)) != hipSuccess)
-      return thipfail(t, "hipMemcpy(x)", e);
+      return hipfail(t, "hipMemcpy(x)", e);
     for (int attempt = 0; attempt < 2; ++attempt)
     {
       t->h_rec.resize(B * static_cast<size_t>(t->rec_cap) * W);
       if (thip_eval_collision(t->ev, 0, t->h_x.data(), t->h_rec.data(), t->rec_cap, t->h_cnt.data()) != THIP_OK)
-        return tfail(t, std::string("thip_eval_collision: ") + thip_eval_last_error(t->ev));
+        return fail(t, std::string("thip_eval_collision: ") + thip_eval_last_error(t->ev));
       const int mx = *std::max_element(t->h_cnt.begin(), t->h_cnt.end());
       if (mx <= t->rec_cap)
         break;
       t->rec_cap = mx;  // a problem had more contacts than the staging holds: once more with room for all
-      hipFree(t->d_rec);
-      t->d_rec = nullptr;
+      drop(*t, t->d_rec);
     }
     // a record names a robot sphere and a primitive or a second sphere: anything else is an
     // error here, not a contact to skip (the kernel's own range test only guards its reads)
@@ -614,42 +597,47 @@ int run_on_device(thip_terms* t, const double* d_x, double* costs, double* viols
         const double* e = t->h_rec.data() + (b * static_cast<size_t>(t->rec_cap) + r) * W;
         const int p = static_cast<int>(e[2]), s = static_cast<int>(e[3]);
         if (s < 0 || s >= t->desc.n_spheres || (p >= 0 ? p >= t->desc.n_prims : -1 - p >= t->desc.n_spheres))
-          return tfail(t, "thip_eval_collision returned a contact record with sphere " + std::to_string(s) +
+          return fail(t, "thip_eval_collision returned a contact record with sphere " + std::to_string(s) +
                               " / other " + std::to_string(p) + " out of range");
       }
-    if (!t->d_rec && (e = hipMalloc(&t->d_rec, B * static_cast<size_t>(t->rec_cap) * W * sizeof(double))) != hipSuccess)
-      return thipfail(t, "hipMalloc(contact records)", e);
+    if (!t->d_rec && (e = alloc(*t, t->d_rec, B * static_cast<size_t>(t->rec_cap) * W)) != hipSuccess)
+      return hipfail(t, "hipMalloc(contact records)", e);
     if ((e = hipMemcpyAsync(t->d_rec, t->h_rec.data(), t->h_rec.size() * sizeof(double), hipMemcpyHostToDevice,
                             t->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(t->d_cnt, t->h_cnt.data(), B * sizeof(int), hipMemcpyHostToDevice, t->stream)) != hipSuccess)
-      return thipfail(t, "hipMemcpy(contact records)", e);
+      return hipfail(t, "hipMemcpy(contact records)", e);
     hipLaunchKernelGGL(coll_reduce_kernel, dim3(static_cast<unsigned>(B * S.n_units)), dim3(kTvBlock), 0, t->stream,
                        t->d_model, t->d_slots, t->d_pair, t->batch, t->d_rec, t->d_cnt, t->rec_cap, W,
                        S.coll_cnt ? t->d_viols : t->d_costs, std::max(S.coll_cnt ? S.n_cnts : S.n_costs, 1));
-    if ((e = hipGetLastError()) != hipSuccess)
-      return thipfail(t, "coll_reduce_kernel launch", e);
+    return launched(t, "coll_reduce_kernel");
   }
-  else if (S.coll && S.n_units > 0)
+  if (S.coll && S.n_units > 0)
   {
     hipLaunchKernelGGL(coll_values_kernel, dim3(static_cast<unsigned>(B * S.n_units)), dim3(kTvBlock), 0, t->stream,
                        &t->d_desc->chain, t->d_model, t->d_slots, t->d_pair, t->batch, d_x, t->d_scene,
                        S.coll_cnt ? t->d_viols : t->d_costs, std::max(S.coll_cnt ? S.n_cnts : S.n_costs, 1));
-    if ((e = hipGetLastError()) != hipSuccess)
-      return thipfail(t, "coll_values_kernel launch", e);
+    return launched(t, "coll_values_kernel");
   }
-  if ((e = hipEventRecord(t->ev1, t->stream)) != hipSuccess)
-    return thipfail(t, "hipEventRecord", e);
-  if ((S.n_costs > 0 && costs &&
-       (e = hipMemcpyAsync(costs, t->d_costs, B * S.n_costs * sizeof(double), hipMemcpyDeviceToHost, t->stream)) !=
-           hipSuccess) ||
-      (S.n_cnts > 0 && viols &&
-       (e = hipMemcpyAsync(viols, t->d_viols, B * S.n_cnts * sizeof(double), hipMemcpyDeviceToHost, t->stream)) !=
-           hipSuccess) ||
-      (e = hipStreamSynchronize(t->stream)) != hipSuccess)
-    return thipfail(t, "term value kernels", e);
-  float ms = -1.0f;
-  t->last_ms = hipEventElapsedTime(&ms, t->ev0, t->ev1) == hipSuccess ? static_cast<double>(ms) : -1.0;
   return THIP_OK;
+}
+
+// thip_terms_run (x on the host) and thip_terms_run_device
+int run(thip_terms* t, bool on_host, const double* x, double* costs, double* viols)
+{
+  if (!t)
+    return THIP_E_INVALID;
+  const Slots& S = t->slots;
+  const size_t B = static_cast<size_t>(t->batch);
+  const double* d_x = nullptr;
+  if (const int rc = stage_x(t, "thip_terms", on_host, x, (S.n_costs == 0 || costs) && (S.n_cnts == 0 || viols),
+                             " / costs / viols", t->d_x, B * S.N * S.D, d_x);
+      rc != THIP_OK)
+    return rc;
+  auto fetch = [&] {
+    const hipError_t e = to_host(t, S.n_costs > 0 ? costs : nullptr, t->d_costs, B * S.n_costs * sizeof(double));
+    return e != hipSuccess ? e : to_host(t, S.n_cnts > 0 ? viols : nullptr, t->d_viols, B * S.n_cnts * sizeof(double));
+  };
+  return timed_run(t, "term value kernels", [&] { return launch_kernels(t, d_x); }, fetch);
 }
 
 int upload_inputs(thip_terms* t, const double* tgt, const double* scene, hipMemcpyKind kind, const char* who)
@@ -659,20 +647,20 @@ int upload_inputs(thip_terms* t, const double* tgt, const double* scene, hipMemc
   const thip_problem_desc& d = t->desc;
   const bool need_scene = d.coll_enabled && d.n_prims > 0;
   if (d.n_cart > 0 && !tgt)
-    return tfail(t, std::string(who) + ": cart_targets required when n_cart > 0");
+    return fail(t, std::string(who) + ": cart_targets required when n_cart > 0");
   if (need_scene && !scene)
-    return tfail(t, std::string(who) + ": scene required when the collision term has primitives");
+    return fail(t, std::string(who) + ": scene required when the collision term has primitives");
   const size_t B = static_cast<size_t>(t->batch);
   hipError_t e;
   if ((e = hipSetDevice(t->device)) != hipSuccess)
-    return thipfail(t, "hipSetDevice", e);
+    return hipfail(t, "hipSetDevice", e);
   if (d.n_cart > 0 && (e = hipMemcpyAsync(t->d_tgt, tgt, B * d.n_cart * 12 * sizeof(double), kind, t->stream)) != hipSuccess)
-    return thipfail(t, "hipMemcpy(cart_targets)", e);
+    return hipfail(t, "hipMemcpy(cart_targets)", e);
   if (need_scene &&
       (e = hipMemcpyAsync(t->d_scene, scene, B * d.n_prims * 16 * sizeof(double), kind, t->stream)) != hipSuccess)
-    return thipfail(t, "hipMemcpy(scene)", e);
+    return hipfail(t, "hipMemcpy(scene)", e);
   if ((e = hipStreamSynchronize(t->stream)) != hipSuccess)
-    return thipfail(t, "hipStreamSynchronize", e);
+    return hipfail(t, "hipStreamSynchronize", e);
   if (t->ev)
   {
     // the FIRST / CLOSEST route's evaluator takes host arrays; it reads no CartPose target
@@ -682,12 +670,12 @@ int upload_inputs(thip_terms* t, const double* tgt, const double* scene, hipMemc
       t->h_scene.resize(B * d.n_prims * 16);
       if ((e = hipMemcpy(t->h_scene.data(), t->d_scene, t->h_scene.size() * sizeof(double), hipMemcpyDeviceToHost)) !=
           hipSuccess)
-        return thipfail(t, "hipMemcpy(scene)", e);
+        return hipfail(t, "hipMemcpy(scene)", e);
       hs = t->h_scene.data();
     }
     const std::vector<double> zeros(B * std::max(d.n_cart, 1) * 12, 0.0);
     if (thip_eval_upload(t->ev, zeros.data(), hs) != THIP_OK)
-      return tfail(t, std::string("thip_eval_upload: ") + thip_eval_last_error(t->ev));
+      return fail(t, std::string("thip_eval_upload: ") + thip_eval_last_error(t->ev));
   }
   t->uploaded = true;
   return THIP_OK;
@@ -698,16 +686,16 @@ int upload_jpt(thip_terms* t, const double* jpt, hipMemcpyKind kind, const char*
   if (!t)
     return THIP_E_INVALID;
   if (!jpt)
-    return tfail(t, std::string(who) + ": null jpos_targets");
+    return fail(t, std::string(who) + ": null jpos_targets");
   if (t->desc.n_jpos == 0)
     return THIP_OK;
   hipError_t e;
   if ((e = hipSetDevice(t->device)) != hipSuccess)
-    return thipfail(t, "hipSetDevice", e);
+    return hipfail(t, "hipSetDevice", e);
   const size_t n = static_cast<size_t>(t->batch) * t->desc.n_jpos * t->desc.chain.n_dof;
   if ((e = hipMemcpyAsync(t->d_jpt, jpt, n * sizeof(double), kind, t->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(t->stream)) != hipSuccess)
-    return thipfail(t, "hipMemcpy(jpos_targets)", e);
+    return hipfail(t, "hipMemcpy(jpos_targets)", e);
   return THIP_OK;
 }
 }  // namespace
@@ -725,16 +713,13 @@ int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip
     g_terms_create_err = "thip_terms_create: null argument or batch <= 0";
     return THIP_E_INVALID;
   }
-  auto reject = [](const std::string& m) {
-    g_terms_create_err = "thip_terms_create: " + m;
-    return THIP_E_INVALID;
-  };
+  const host::CreateError reject{ g_terms_create_err, "thip_terms_create: " };
   {
     std::string why;
     if (const lowering::Finding f = lowering::validate(*desc, why))
       return reject(why + kTermsWording[f]);
   }
-  auto* t = new thip_terms();
+  std::unique_ptr<thip_terms, void (*)(thip_terms*)> t(new thip_terms(), thip_terms_destroy);
   t->device = device;
   t->batch = batch;
   t->desc = *desc;
@@ -748,31 +733,16 @@ int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip
   }
   const Slots& S = t->slots;
   if (static_cast<long long>(std::max(S.n_units, 1)) * batch > INT_MAX)
-  {
-    delete t;
     return reject("batch * collision units exceeds the grid");
-  }
   Model md{};
   std::vector<double> ptab;
   if (d.coll_enabled)
   {
     std::vector<int> ssa, ssb, skp;
     self_sphere_pairs(d, ssa, ssb, skp);
-    md.n_sph = d.n_spheres;
+    lowering::fill_sphere_model(d, ssa, ssb, md);
     md.n_prims = d.n_prims;
     lowering::store_sphere_groups(lowering::group_spheres_by_link(d), md);
-    md.n_self_sph = static_cast<int>(ssa.size());
-    for (size_t j = 0; j < ssa.size(); ++j)
-    {
-      md.self_sa[j] = ssa[j];
-      md.self_sb[j] = ssb[j];
-    }
-    for (int s = 0; s < d.n_spheres; ++s)
-    {
-      md.radius[s] = d.sphere_radius[s];
-      for (int i = 0; i < 3; ++i)
-        md.center[s][i] = d.sphere_center[s][i];
-    }
     md.continuous = d.coll_continuous == 1;
     md.lvs = d.coll_lvs;
     md.margin = d.coll_margin;
@@ -780,33 +750,24 @@ int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip
     md.buffer = d.coll_buffer;
     coll_pair_table(d, 0, ptab);
   }
-  auto hfail = [&](const char* what, hipError_t e) {
-    g_terms_create_err = std::string("thip_terms_create: ") + what + ": " + hipGetErrorString(e);
-    thip_terms_destroy(t);
-    return THIP_E_HIP;
-  };
   hipError_t e;
   if ((e = hipSetDevice(device)) != hipSuccess)
-    return hfail("hipSetDevice", e);
+    return reject.hip("hipSetDevice", e);
   const size_t B = static_cast<size_t>(batch), D = static_cast<size_t>(S.D);
   const size_t n_tgt = B * std::max(d.n_cart, 1) * 12, n_scene = B * std::max(d.n_prims, 1) * 16;
   const size_t per_jpt = std::max(d.n_jpos, 1) * D;
   const size_t n_c = B * std::max(S.n_costs, 1), n_v = B * std::max(S.n_cnts, 1);
-  if ((e = hipMalloc(&t->d_desc, sizeof(thip_problem_desc))) != hipSuccess ||
-      (e = hipMalloc(&t->d_slots, sizeof(Slots))) != hipSuccess ||
-      (e = hipMalloc(&t->d_model, sizeof(Model))) != hipSuccess ||
-      (e = hipMalloc(&t->d_tgt, n_tgt * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&t->d_scene, n_scene * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&t->d_jpt, B * per_jpt * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&t->d_x, B * S.N * D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&t->d_costs, n_c * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&t->d_viols, n_v * sizeof(double))) != hipSuccess ||
-      (!ptab.empty() && (e = hipMalloc(&t->d_pair, ptab.size() * sizeof(double))) != hipSuccess))
-    return hfail("hipMalloc", e);
-  if ((e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking)) != hipSuccess)
-    return hfail("hipStreamCreate", e);
-  if ((e = hipEventCreate(&t->ev0)) != hipSuccess || (e = hipEventCreate(&t->ev1)) != hipSuccess)
-    return hfail("hipEventCreate", e);
+  if ((e = alloc(*t, t->d_desc, 1)) != hipSuccess || (e = alloc(*t, t->d_slots, 1)) != hipSuccess ||
+      (e = alloc(*t, t->d_model, 1)) != hipSuccess || (e = alloc(*t, t->d_tgt, n_tgt)) != hipSuccess ||
+      (e = alloc(*t, t->d_scene, n_scene)) != hipSuccess || (e = alloc(*t, t->d_jpt, B * per_jpt)) != hipSuccess ||
+      (e = alloc(*t, t->d_x, B * S.N * D)) != hipSuccess || (e = alloc(*t, t->d_costs, n_c)) != hipSuccess ||
+      (e = alloc(*t, t->d_viols, n_v)) != hipSuccess ||
+      (!ptab.empty() && (e = alloc(*t, t->d_pair, ptab.size())) != hipSuccess))
+    return reject.hip("hipMalloc", e);
+  if ((e = open_stream(*t)) != hipSuccess)
+    return reject.hip("hipStreamCreate", e);
+  if ((e = open_events(*t)) != hipSuccess)
+    return reject.hip("hipEventCreate", e);
   // every problem starts with the descriptor's JointPos targets
   std::vector<double> jpt(B * per_jpt, 0.0);
   for (size_t b = 0; b < B; ++b)
@@ -826,7 +787,7 @@ int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip
       (e = hipMemsetAsync(t->d_costs, 0, n_c * sizeof(double), t->stream)) != hipSuccess ||
       (e = hipMemsetAsync(t->d_viols, 0, n_v * sizeof(double), t->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(t->stream)) != hipSuccess)
-    return hfail("hipMemcpy", e);
+    return reject.hip("hipMemcpy", e);
   // nothing to upload: the evaluator is ready
   t->uploaded = d.n_cart == 0 && !(d.coll_enabled && d.n_prims > 0);
   if (d.coll_enabled && d.coll_contact_test != THIP_CONTACT_ALL)
@@ -834,20 +795,18 @@ int thip_terms_create(int device, const thip_problem_desc* desc, int batch, thip
     if (thip_eval_create(device, &t->desc, batch, &t->ev) != THIP_OK)
     {
       g_terms_create_err = std::string("thip_terms_create: ") + thip_eval_last_error(nullptr);
-      thip_terms_destroy(t);
       return THIP_E_HIP;
     }
     t->rec_cap = 256;
-    if ((e = hipMalloc(&t->d_cnt, B * sizeof(int))) != hipSuccess)
-      return hfail("hipMalloc", e);
+    if ((e = alloc(*t, t->d_cnt, B)) != hipSuccess)
+      return reject.hip("hipMalloc", e);
     if (t->uploaded && thip_eval_upload(t->ev, nullptr, nullptr) != THIP_OK)
     {
       g_terms_create_err = std::string("thip_terms_create: ") + thip_eval_last_error(t->ev);
-      thip_terms_destroy(t);
       return THIP_E_HIP;
     }
   }
-  *out = t;
+  *out = t.release();
   return THIP_OK;
 }
 
@@ -917,33 +876,12 @@ int thip_terms_upload_joint_targets_device(thip_terms* t, const double* d_jpos_t
 
 int thip_terms_run(thip_terms* t, const double* x, double* costs, double* viols)
 {
-  if (!t)
-    return THIP_E_INVALID;
-  if (!x || (t->slots.n_costs > 0 && !costs) || (t->slots.n_cnts > 0 && !viols))
-    return tfail(t, "thip_terms_run: null x / costs / viols");
-  if (!t->uploaded)
-    return tfail(t, "thip_terms_run: thip_terms_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(t->device)) != hipSuccess)
-    return thipfail(t, "hipSetDevice", e);
-  const size_t n = static_cast<size_t>(t->batch) * t->slots.N * t->slots.D;
-  if ((e = hipMemcpyAsync(t->d_x, x, n * sizeof(double), hipMemcpyHostToDevice, t->stream)) != hipSuccess)
-    return thipfail(t, "hipMemcpy(x)", e);
-  return run_on_device(t, t->d_x, costs, viols);
+  return run(t, true, x, costs, viols);
 }
 
 int thip_terms_run_device(thip_terms* t, const double* d_x, double* costs, double* viols)
 {
-  if (!t)
-    return THIP_E_INVALID;
-  if (!d_x || (t->slots.n_costs > 0 && !costs) || (t->slots.n_cnts > 0 && !viols))
-    return tfail(t, "thip_terms_run_device: null d_x / costs / viols");
-  if (!t->uploaded)
-    return tfail(t, "thip_terms_run_device: thip_terms_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(t->device)) != hipSuccess)
-    return thipfail(t, "hipSetDevice", e);
-  return run_on_device(t, d_x, costs, viols);
+  return run(t, false, d_x, costs, viols);
 }
 
 double thip_terms_last_ms(thip_terms* t) { return t ? t->last_ms : -1.0; }
@@ -952,28 +890,8 @@ void thip_terms_destroy(thip_terms* t)
 {
   if (!t)
     return;
-  hipSetDevice(t->device);
-  if (t->stream)
-    hipStreamSynchronize(t->stream);
-  hipFree(t->d_desc);
-  hipFree(t->d_slots);
-  hipFree(t->d_model);
-  hipFree(t->d_pair);
-  hipFree(t->d_tgt);
-  hipFree(t->d_scene);
-  hipFree(t->d_jpt);
-  hipFree(t->d_x);
-  hipFree(t->d_costs);
-  hipFree(t->d_viols);
-  hipFree(t->d_rec);
-  hipFree(t->d_cnt);
+  release(*t);
   thip_eval_destroy(t->ev);
-  if (t->ev0)
-    hipEventDestroy(t->ev0);
-  if (t->ev1)
-    hipEventDestroy(t->ev1);
-  if (t->stream)
-    hipStreamDestroy(t->stream);
   delete t;
 }
 

@@ -10,12 +10,14 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 #include <cstdlib>
 #include <functional>
 
 #include "desc_lowering.hpp"
+#include "device_handle.hpp"
 #include "layout.hpp"
 
 namespace thip
@@ -32,10 +34,8 @@ __global__ void coll_rows_kernel_gen(KernelArgs args, const double* xin, double*
 
 using namespace thip;
 
-struct thip_ctx
+struct thip_ctx : thip::host::Handle  // stream: its own, or the caller's (thip_set_stream)
 {
-  int device = 0;
-  int batch = 0;
   thip_problem_desc desc{};
   Layout L{};
   // device buffers
@@ -52,14 +52,10 @@ struct thip_ctx
   double* d_scene = nullptr;
   double* d_jpt = nullptr;   // JointPos targets [batch][max(n_jpos,1)][D]
   double* d_x = nullptr;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double* d_trace = nullptr;
   int* d_trace_n = nullptr;
   int trace_cap = 0;
   long long* d_prof = nullptr;
-  bool uploaded = false;
   bool ran = false;
   size_t lds_bytes = 0;      // sqp_kernel: scratch + LDS-resident arrays
   size_t lds_lin_bytes = 0;  // linearize_kernel: scratch only
@@ -67,21 +63,21 @@ struct thip_ctx
   int grid = 0;              // sqp_kernel workgroups (resident slots, or the batch)
   bool gen = false;          // the QPs never take the segment: launch the generic-step build
                              // (sqp_kernel_gen, kGenBlock threads) instead of sqp_kernel
-  std::string err;
 };
 
 static thread_local std::string g_create_err;
 
-#define HIPCHK(ctx, call)                                                            \
-  do                                                                                 \
-  {                                                                                  \
-    hipError_t e_ = (call);                                                          \
-    if (e_ != hipSuccess)                                                            \
-    {                                                                                \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-      return THIP_E_HIP;                                                             \
-    }                                                                                \
+// text: what a failure is reported under (HIPCHK: the call as written).  The
+// literals passed to HIPCHK_AS are the messages callers have always seen, kept
+// byte for byte: frozen text, not a description of the call beside them.
+#define HIPCHK_AS(ctx, call, text)                            \
+  do                                                          \
+  {                                                           \
+    const hipError_t e_ = (call);                             \
+    if (e_ != hipSuccess)                                     \
+      return thip::host::hipfail((ctx), (text), e_);          \
   } while (0)
+#define HIPCHK(ctx, call) HIPCHK_AS(ctx, call, #call)
 
 extern "C" {
 
@@ -180,6 +176,8 @@ static const char* const kCreateWording[lowering::kFindingCount] = {
 
 int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx** out)
 {
+  if (out)
+    *out = nullptr;
   if (!desc || !out || batch <= 0)
   {
     g_create_err = "thip_create: null argument or batch <= 0";
@@ -191,7 +189,7 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     g_create_err = "thip_create: " + why + kCreateWording[f];
     return THIP_E_INVALID;
   }
-  auto* ctx = new thip_ctx();
+  std::unique_ptr<thip_ctx, void (*)(thip_ctx*)> ctx(new thip_ctx(), thip_destroy);
   ctx->device = device;
   ctx->batch = batch;
   ctx->desc = *desc;
@@ -523,7 +521,6 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     if (sizes[k] < 0)
     {
       g_create_err = "internal: workspace size table incomplete";
-      delete ctx;
       return THIP_E_INVALID;
     }
   long long off = 0;
@@ -623,7 +620,6 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     if (L.loff[A_LINV] < 0 || L.loff[A_CV] < 0 || L.loff[A_YV] < 0)
     {
       g_create_err = "thip_create: problem too large, the block-solve factor does not fit in LDS";
-      delete ctx;
       return THIP_E_INVALID;
     }
     ctx->lds_bytes = static_cast<size_t>(used) * sizeof(double);
@@ -652,24 +648,20 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     }
   }
 
-  auto fail = [&](const std::string& msg) {
-    g_create_err = msg;
-    thip_destroy(ctx);
-    return THIP_E_HIP;
-  };
+  const host::CreateError bad{ g_create_err, "thip_create: " };
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess)
-    return fail(std::string("hipSetDevice: ") + hipGetErrorString(e));
+    return bad.hip("hipSetDevice", e);
   {
     // BasicTrustRegionSQPParameters::max_time (seconds) in wall_clock64() ticks
     int rate_khz = 0;
     if ((e = hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device)) != hipSuccess || rate_khz <= 0)
-      return fail("hipDeviceGetAttribute(WallClockRate) failed");
+      return g_create_err = "hipDeviceGetAttribute(WallClockRate) failed", THIP_E_HIP;
     const double ticks = d.sqp.max_time * 1e3 * static_cast<double>(rate_khz);
     L.max_ticks = (ticks >= 9.0e18) ? LLONG_MAX : (ticks <= 0 ? 0LL : static_cast<long long>(ticks));
   }
   if (ctx->lds_lin_bytes > 60 * 1024)
-    return fail("problem too large for the LDS-resident block solve");
+    return g_create_err = "problem too large for the LDS-resident block solve", THIP_E_HIP;
   // tables
   std::vector<int> itab;
   auto push = [&](const std::vector<int>& v, size_t n) {
@@ -712,10 +704,9 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
                o_ssa = push(self_sa, self_sa.size()), o_ssb = push(self_sb, self_sb.size()),
                o_skp = push(self_kp, self_kp.size());
   row_w.resize(std::max<size_t>(na, 1));
-  if ((e = hipMalloc(&ctx->d_tables, itab.size() * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_tables_f, row_w.size() * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_desc, sizeof(thip_problem_desc))) != hipSuccess)
-    return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
+  if ((e = alloc(*ctx, ctx->d_tables, itab.size())) != hipSuccess ||
+      (e = alloc(*ctx, ctx->d_tables_f, row_w.size())) != hipSuccess || (e = alloc(*ctx, ctx->d_desc, 1)) != hipSuccess)
+    return bad.hip("hipMalloc", e);
   hipMemcpy(ctx->d_tables, itab.data(), itab.size() * sizeof(int), hipMemcpyHostToDevice);
   hipMemcpy(ctx->d_tables_f, row_w.data(), row_w.size() * sizeof(double), hipMemcpyHostToDevice);
   hipMemcpy(ctx->d_desc, &ctx->desc, sizeof(thip_problem_desc), hipMemcpyHostToDevice);
@@ -767,23 +758,21 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     std::vector<double> ptab;
     if (L.coll && coll_pair_table(d, 0, ptab))
     {
-      if ((e = hipMalloc(&ctx->d_pair, ptab.size() * sizeof(double))) != hipSuccess ||
+      if ((e = alloc(*ctx, ctx->d_pair, ptab.size())) != hipSuccess ||
           (e = hipMemcpy(ctx->d_pair, ptab.data(), ptab.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess)
-        return fail(std::string("hipMalloc(pair table): ") + hipGetErrorString(e));
+        return bad.hip("hipMalloc(pair table)", e);
       T.pair_mc = ctx->d_pair;
     }
   }
   const size_t B = static_cast<size_t>(batch);
-  if ((e = hipMalloc(&ctx->d_ws, B * static_cast<size_t>(L.dstride) * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_iws, B * static_cast<size_t>(L.istride) * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_res, B * sizeof(thip_result))) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_init, B * static_cast<size_t>(nx) * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_tgt, B * static_cast<size_t>(std::max(L.n_cart, 1)) * 12 * sizeof(double))) !=
-          hipSuccess ||
-      (e = hipMalloc(&ctx->d_x, B * static_cast<size_t>(nx) * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&ctx->d_jpt, B * static_cast<size_t>(std::max(L.n_jpos, 1) * L.D) * sizeof(double))) !=
-          hipSuccess)
-    return fail(std::string("hipMalloc(workspace): ") + hipGetErrorString(e));
+  if ((e = alloc(*ctx, ctx->d_ws, B * static_cast<size_t>(L.dstride))) != hipSuccess ||
+      (e = alloc(*ctx, ctx->d_iws, B * static_cast<size_t>(L.istride))) != hipSuccess ||
+      (e = alloc(*ctx, ctx->d_res, B)) != hipSuccess ||
+      (e = alloc(*ctx, ctx->d_init, B * static_cast<size_t>(nx))) != hipSuccess ||
+      (e = alloc(*ctx, ctx->d_tgt, B * static_cast<size_t>(std::max(L.n_cart, 1)) * 12)) != hipSuccess ||
+      (e = alloc(*ctx, ctx->d_x, B * static_cast<size_t>(nx))) != hipSuccess ||
+      (e = alloc(*ctx, ctx->d_jpt, B * static_cast<size_t>(std::max(L.n_jpos, 1) * L.D))) != hipSuccess)
+    return bad.hip("hipMalloc(workspace)", e);
   {
     // every problem starts with the descriptor's JointPos targets
     const size_t per = static_cast<size_t>(std::max(L.n_jpos, 1) * L.D);
@@ -793,11 +782,10 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
         for (int j = 0; j < L.D; ++j)
           jpt[b * per + static_cast<size_t>(k * L.D + j)] = d.jpos_targets[k][j];
     if ((e = hipMemcpy(ctx->d_jpt, jpt.data(), jpt.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess)
-      return fail(std::string("hipMemcpy(jpos targets): ") + hipGetErrorString(e));
+      return bad.hip("hipMemcpy(jpos targets)", e);
   }
-  if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess)
-    return fail(std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  ctx->own_stream = true;
+  if ((e = open_stream(*ctx)) != hipSuccess)
+    return bad.hip("hipStreamCreate", e);
   // zeroed on the context's own (non-blocking) stream and waited for here: a
   // non-blocking stream does not order against the null stream, and the
   // caller may swap in its own stream (thip_set_stream) before the first run
@@ -805,9 +793,9 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
           hipSuccess ||
       (e = hipMemsetAsync(ctx->d_res, 0, B * sizeof(thip_result), ctx->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
-    return fail(std::string("hipMemsetAsync(workspace): ") + hipGetErrorString(e));
-  if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess || (e = hipEventCreate(&ctx->ev1)) != hipSuccess)
-    return fail(std::string("hipEventCreate: ") + hipGetErrorString(e));
+    return bad.hip("hipMemsetAsync(workspace)", e);
+  if ((e = open_events(*ctx)) != hipSuccess)
+    return bad.hip("hipEventCreate", e);
   const void* fused = ctx->gen ? reinterpret_cast<const void*>(&sqp_kernel_gen) : reinterpret_cast<const void*>(&sqp_kernel);
   const int fused_block = ctx->gen ? kGenBlock : kBlock;
   if ((e = hipFuncSetAttribute(fused, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ctx->lds_bytes))) !=
@@ -815,7 +803,7 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
       (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linearize_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(ctx->lds_lin_bytes))) !=
           hipSuccess)
-    return fail(std::string("hipFuncSetAttribute(dynamic LDS): ") + hipGetErrorString(e));
+    return bad.hip("hipFuncSetAttribute(dynamic LDS)", e);
   // dynamic problem assignment: one persistent workgroup per resident slot
   // (KernelArgs::work), unless THIP_DEBUG_STATIC_DISPATCH is set (one workgroup per problem)
   ctx->grid = batch;
@@ -824,18 +812,18 @@ int thip_create(int device, const thip_problem_desc* desc, int batch, thip_ctx**
     int per_cu = 0, n_cu = 0;
     if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused, fused_block, ctx->lds_bytes)) != hipSuccess ||
         (e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess)
-      return fail(std::string("occupancy query: ") + hipGetErrorString(e));
+      return bad.hip("occupancy query", e);
     const long long slots = static_cast<long long>(std::max(per_cu, 1)) * std::max(n_cu, 1);
     if (slots < batch)
     {
-      if ((e = hipMalloc(&ctx->d_work, 2 * sizeof(int))) != hipSuccess ||
+      if ((e = alloc(*ctx, ctx->d_work, 2)) != hipSuccess ||
           (e = hipMemsetAsync(ctx->d_work, 0, 2 * sizeof(int), ctx->stream)) != hipSuccess ||
           (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
-        return fail(std::string("work counter: ") + hipGetErrorString(e));
+        return bad.hip("work counter", e);
       ctx->grid = static_cast<int>(slots);
     }
   }
-  *out = ctx;
+  *out = ctx.release();
   return THIP_OK;
 }
 
@@ -845,10 +833,10 @@ int thip_set_stream(thip_ctx* ctx, void* stream)
     return THIP_E_INVALID;
   if (stream == nullptr)
     return THIP_OK;
-  if (ctx->own_stream && ctx->stream)
+  if (ctx->owns_stream && ctx->stream)
     hipStreamDestroy(ctx->stream);
   ctx->stream = static_cast<hipStream_t>(stream);
-  ctx->own_stream = false;
+  ctx->owns_stream = false;
   return THIP_OK;
 }
 
@@ -905,7 +893,7 @@ static int upload_scene(thip_ctx* ctx, const double* scene, hipMemcpyKind kind)
     return ctx->err = "thip_upload: scene required when collision is enabled", THIP_E_INVALID;
   const size_t bytes = static_cast<size_t>(ctx->batch) * std::max(ctx->desc.n_prims, 1) * 16 * sizeof(double);
   if (!ctx->d_scene)
-    HIPCHK(ctx, hipMalloc(&ctx->d_scene, bytes));
+    HIPCHK_AS(ctx, alloc(*ctx, ctx->d_scene, bytes / sizeof(double)), "hipMalloc(&ctx->d_scene, bytes)");
   if (ctx->desc.n_prims > 0)
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_scene, scene, bytes, kind, ctx->stream));
   return THIP_OK;
@@ -1029,11 +1017,11 @@ int thip_linearize(thip_ctx* ctx, const double* x, double* err, double* jac)
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t B = static_cast<size_t>(ctx->batch);
   const Layout& L = ctx->L;
-  double *dx = nullptr, *de = nullptr, *dj = nullptr;
+  host::Scoped<double> dx, de, dj;
   const size_t ne = B * static_cast<size_t>(L.n_cart) * 6, nj = ne * static_cast<size_t>(L.D);
-  HIPCHK(ctx, hipMalloc(&dx, B * static_cast<size_t>(L.nx) * sizeof(double)));
-  HIPCHK(ctx, hipMalloc(&de, std::max<size_t>(ne, 1) * sizeof(double)));
-  HIPCHK(ctx, hipMalloc(&dj, std::max<size_t>(nj, 1) * sizeof(double)));
+  HIPCHK_AS(ctx, dx.alloc(B * static_cast<size_t>(L.nx)), "hipMalloc(&dx, B * static_cast<size_t>(L.nx) * sizeof(double))");
+  HIPCHK_AS(ctx, de.alloc(std::max<size_t>(ne, 1)), "hipMalloc(&de, std::max<size_t>(ne, 1) * sizeof(double))");
+  HIPCHK_AS(ctx, dj.alloc(std::max<size_t>(nj, 1)), "hipMalloc(&dj, std::max<size_t>(nj, 1) * sizeof(double))");
   hipMemcpyAsync(dx, x, B * static_cast<size_t>(L.nx) * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
   KernelArgs a = make_args(ctx);
   hipLaunchKernelGGL(linearize_kernel, dim3(ctx->batch), dim3(kBlock), ctx->lds_lin_bytes, ctx->stream, a, dx, de, dj);
@@ -1044,9 +1032,6 @@ int thip_linearize(thip_ctx* ctx, const double* x, double* err, double* jac)
     hipMemcpyAsync(jac, dj, nj * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     e = hipStreamSynchronize(ctx->stream);
   }
-  hipFree(dx);
-  hipFree(de);
-  hipFree(dj);
   if (e != hipSuccess)
     return ctx->err = std::string("thip_linearize: ") + hipGetErrorString(e), THIP_E_HIP;
   return THIP_OK;
@@ -1060,9 +1045,9 @@ int thip_fwd_kin(thip_ctx* ctx, const double* x, double* poses)
   const size_t B = static_cast<size_t>(ctx->batch);
   const Layout& L = ctx->L;
   const size_t np = B * static_cast<size_t>(L.N) * static_cast<size_t>(L.n_links) * 12;
-  double *dx = nullptr, *dp = nullptr;
-  HIPCHK(ctx, hipMalloc(&dx, B * static_cast<size_t>(L.nx) * sizeof(double)));
-  HIPCHK(ctx, hipMalloc(&dp, np * sizeof(double)));
+  host::Scoped<double> dx, dp;
+  HIPCHK_AS(ctx, dx.alloc(B * static_cast<size_t>(L.nx)), "hipMalloc(&dx, B * static_cast<size_t>(L.nx) * sizeof(double))");
+  HIPCHK_AS(ctx, dp.alloc(np), "hipMalloc(&dp, np * sizeof(double))");
   hipMemcpyAsync(dx, x, B * static_cast<size_t>(L.nx) * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
   KernelArgs a = make_args(ctx);
   hipLaunchKernelGGL(fwd_kin_kernel, dim3(ctx->batch), dim3(kBlock), 0, ctx->stream, a, dx, dp);
@@ -1072,8 +1057,6 @@ int thip_fwd_kin(thip_ctx* ctx, const double* x, double* poses)
     hipMemcpyAsync(poses, dp, np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     e = hipStreamSynchronize(ctx->stream);
   }
-  hipFree(dx);
-  hipFree(dp);
   if (e != hipSuccess)
     return ctx->err = std::string("thip_fwd_kin: ") + hipGetErrorString(e), THIP_E_HIP;
   return THIP_OK;
@@ -1084,18 +1067,15 @@ int thip_debug_trace(thip_ctx* ctx, int capacity)
   if (!ctx || capacity < 0)
     return THIP_E_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->d_trace)
-    hipFree(ctx->d_trace);
-  if (ctx->d_trace_n)
-    hipFree(ctx->d_trace_n);
-  ctx->d_trace = nullptr;
-  ctx->d_trace_n = nullptr;
+  drop(*ctx, ctx->d_trace);
+  drop(*ctx, ctx->d_trace_n);
   ctx->trace_cap = capacity;
   if (capacity == 0)
     return THIP_OK;
   const size_t B = static_cast<size_t>(ctx->batch);
-  HIPCHK(ctx, hipMalloc(&ctx->d_trace, B * static_cast<size_t>(capacity) * THIP_TRACE_W * sizeof(double)));
-  HIPCHK(ctx, hipMalloc(&ctx->d_trace_n, B * sizeof(int)));
+  HIPCHK_AS(ctx, alloc(*ctx, ctx->d_trace, B * static_cast<size_t>(capacity) * THIP_TRACE_W),
+            "hipMalloc(&ctx->d_trace, B * static_cast<size_t>(capacity) * THIP_TRACE_W * sizeof(double))");
+  HIPCHK_AS(ctx, alloc(*ctx, ctx->d_trace_n, B), "hipMalloc(&ctx->d_trace_n, B * sizeof(int))");
   // ordered with the runs on the context's stream (non-blocking: the null
   // stream would not order against it)
   HIPCHK(ctx, hipMemsetAsync(ctx->d_trace_n, 0, B * sizeof(int), ctx->stream));
@@ -1144,18 +1124,12 @@ int thip_collision_rows(thip_ctx* ctx, const double* x, double* records, int cap
   const size_t B = static_cast<size_t>(ctx->batch);
   const Layout& L = ctx->L;
   const size_t W = 8 + 2 * static_cast<size_t>(L.D) + 1;
-  double *dx = nullptr, *dout = nullptr;
-  int* dcnt = nullptr;
+  host::Scoped<double> dx, dout;
+  host::Scoped<int> dcnt;
   hipError_t e;
-  if ((e = hipMalloc(&dx, B * L.nx * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&dout, B * static_cast<size_t>(cap) * W * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&dcnt, B * sizeof(int))) != hipSuccess)
-  {
-    hipFree(dx);
-    hipFree(dout);
-    hipFree(dcnt);
+  if ((e = dx.alloc(B * L.nx)) != hipSuccess || (e = dout.alloc(B * static_cast<size_t>(cap) * W)) != hipSuccess ||
+      (e = dcnt.alloc(B)) != hipSuccess)
     return ctx->err = std::string("thip_collision_rows: hipMalloc: ") + hipGetErrorString(e), THIP_E_NOMEM;
-  }
   hipMemcpyAsync(dx, x, B * L.nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
   hipMemsetAsync(dout, 0, B * static_cast<size_t>(cap) * W * sizeof(double), ctx->stream);
   KernelArgs a = make_args(ctx);
@@ -1172,9 +1146,6 @@ int thip_collision_rows(thip_ctx* ctx, const double* x, double* records, int cap
     e = hipMemcpyAsync(counts, dcnt, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess)
     e = hipStreamSynchronize(ctx->stream);
-  hipFree(dx);
-  hipFree(dout);
-  hipFree(dcnt);
   if (e != hipSuccess)
     return ctx->err = std::string("thip_collision_rows: ") + hipGetErrorString(e), THIP_E_HIP;
   return THIP_OK;
@@ -1185,13 +1156,11 @@ int thip_debug_profile(thip_ctx* ctx, int enable)
   if (!ctx)
     return THIP_E_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->d_prof)
-    hipFree(ctx->d_prof);
-  ctx->d_prof = nullptr;
+  drop(*ctx, ctx->d_prof);
   if (!enable)
     return THIP_OK;
   const size_t n = static_cast<size_t>(ctx->batch) * kProfSlots;
-  HIPCHK(ctx, hipMalloc(&ctx->d_prof, n * sizeof(long long)));
+  HIPCHK_AS(ctx, alloc(*ctx, ctx->d_prof, n), "hipMalloc(&ctx->d_prof, n * sizeof(long long))");
   HIPCHK(ctx, hipMemsetAsync(ctx->d_prof, 0, n * sizeof(long long), ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return THIP_OK;
@@ -1224,30 +1193,7 @@ void thip_destroy(thip_ctx* ctx)
 {
   if (!ctx)
     return;
-  hipSetDevice(ctx->device);
-  if (ctx->stream)
-    hipStreamSynchronize(ctx->stream);
-  hipFree(ctx->d_desc);
-  hipFree(ctx->d_tables);
-  hipFree(ctx->d_tables_f);
-  hipFree(ctx->d_pair);
-  hipFree(ctx->d_ws);
-  hipFree(ctx->d_iws);
-  hipFree(ctx->d_res);
-  hipFree(ctx->d_work);
-  hipFree(ctx->d_init);
-  hipFree(ctx->d_tgt);
-  hipFree(ctx->d_scene);
-  hipFree(ctx->d_jpt);
-  hipFree(ctx->d_x);
-  hipFree(ctx->d_trace);
-  hipFree(ctx->d_trace_n);
-  if (ctx->ev0)
-    hipEventDestroy(ctx->ev0);
-  if (ctx->ev1)
-    hipEventDestroy(ctx->ev1);
-  if (ctx->own_stream && ctx->stream)
-    hipStreamDestroy(ctx->stream);
+  release(*ctx);
   delete ctx;
 }
 

@@ -25,11 +25,13 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "collision_device.hpp"
 #include "desc_lowering.hpp"
+#include "device_handle.hpp"
 #include "kin_device.hpp"
 
 namespace thip
@@ -364,9 +366,8 @@ __global__ __launch_bounds__(64) void traj_fold_kernel(const UnitRec* recs, Para
 
 using namespace thip::chk;
 
-struct thip_check
+struct thip_check : thip::host::Handle
 {
-  int device = 0, batch = 0;
   Params pr{};
   int D = 0;
   thip_chain* d_chain = nullptr;
@@ -376,52 +377,36 @@ struct thip_check
   UnitRec* d_recs = nullptr;
   double* d_unit_min = nullptr;
   thip_check_result* d_results = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool uploaded = false;
-  double last_ms = -1.0;
-  std::string err;
 };
 
 static thread_local std::string g_check_create_err;
 
 namespace
 {
-int cfail(thip_check* c, const std::string& m)
+// thip_check_run (x on the host) and thip_check_run_device
+int run(thip_check* c, bool on_host, const double* x, thip_check_result* results, double* unit_min)
 {
-  c->err = m;
-  return THIP_E_INVALID;
-}
-int chipfail(thip_check* c, const char* what, hipError_t e)
-{
-  c->err = std::string(what) + ": " + hipGetErrorString(e);
-  return THIP_E_HIP;
-}
-
-int run_on_device(thip_check* c, const double* d_x, thip_check_result* results, double* unit_min)
-{
+  if (!c)
+    return THIP_E_INVALID;
   const size_t B = static_cast<size_t>(c->batch), nu = static_cast<size_t>(c->pr.n_units);
-  hipError_t e;
-  if ((e = hipEventRecord(c->ev0, c->stream)) != hipSuccess)
-    return chipfail(c, "hipEventRecord", e);
-  hipLaunchKernelGGL(traj_check_kernel, dim3(static_cast<unsigned>(B * nu)), dim3(kBlock), 0, c->stream, c->d_chain,
-                     c->d_model, c->pr, d_x, c->d_scene, c->d_recs, c->d_unit_min);
-  if ((e = hipGetLastError()) != hipSuccess)
-    return chipfail(c, "traj_check_kernel launch", e);
-  hipLaunchKernelGGL(traj_fold_kernel, dim3(c->batch), dim3(64), 0, c->stream, c->d_recs, c->pr, c->d_results);
-  if ((e = hipGetLastError()) != hipSuccess)
-    return chipfail(c, "traj_fold_kernel launch", e);
-  if ((e = hipEventRecord(c->ev1, c->stream)) != hipSuccess)
-    return chipfail(c, "hipEventRecord", e);
-  if ((e = hipMemcpyAsync(results, c->d_results, B * sizeof(thip_check_result), hipMemcpyDeviceToHost, c->stream)) !=
-          hipSuccess ||
-      (unit_min && (e = hipMemcpyAsync(unit_min, c->d_unit_min, B * nu * sizeof(double), hipMemcpyDeviceToHost,
-                                       c->stream)) != hipSuccess) ||
-      (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-    return chipfail(c, "traj_check_kernel", e);
-  float ms = -1.0f;
-  c->last_ms = hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess ? static_cast<double>(ms) : -1.0;
-  return THIP_OK;
+  const double* d_x = nullptr;
+  if (const int rc = stage_x(c, "thip_check", on_host, x, results != nullptr, " / results", c->d_x,
+                             B * static_cast<size_t>(c->pr.N) * c->D, d_x);
+      rc != THIP_OK)
+    return rc;
+  auto launch = [&] {
+    hipLaunchKernelGGL(traj_check_kernel, dim3(static_cast<unsigned>(B * nu)), dim3(kBlock), 0, c->stream, c->d_chain,
+                       c->d_model, c->pr, d_x, c->d_scene, c->d_recs, c->d_unit_min);
+    if (const int rc = launched(c, "traj_check_kernel"); rc != THIP_OK)
+      return rc;
+    hipLaunchKernelGGL(traj_fold_kernel, dim3(c->batch), dim3(64), 0, c->stream, c->d_recs, c->pr, c->d_results);
+    return launched(c, "traj_fold_kernel");
+  };
+  auto fetch = [&] {
+    const hipError_t e = to_host(c, results, c->d_results, B * sizeof(thip_check_result));
+    return e != hipSuccess ? e : to_host(c, unit_min, c->d_unit_min, B * nu * sizeof(double));
+  };
+  return timed_run(c, "traj_check_kernel", launch, fetch);
 }
 }  // namespace
 
@@ -451,10 +436,7 @@ int thip_check_create(int device, const thip_problem_desc* desc, const thip_chec
     g_check_create_err = "thip_check_create: null argument or batch <= 0";
     return THIP_E_INVALID;
   }
-  auto reject = [](const std::string& m) {
-    g_check_create_err = "thip_check_create: " + m;
-    return THIP_E_INVALID;
-  };
+  const thip::host::CreateError reject{ g_check_create_err, "thip_check_create: " };
   {
     const std::string why = thip::lowering::abi_mismatch(*desc);
     if (!why.empty())
@@ -499,7 +481,7 @@ int thip_check_create(int device, const thip_problem_desc* desc, const thip_chec
       return reject(why);
   }
 
-  auto* c = new thip_check();
+  std::unique_ptr<thip_check, void (*)(thip_check*)> c(new thip_check(), thip_check_destroy);
   c->device = device;
   c->batch = batch;
   c->D = ch.n_dof;
@@ -517,52 +499,34 @@ int thip_check_create(int device, const thip_problem_desc* desc, const thip_chec
   Model md{};
   {
     const thip_problem_desc& d = *desc;
-    md.n_sph = d.n_spheres;
+    thip::lowering::fill_sphere_model(d, ssa, ssb, md);
+    std::copy(d.sphere_link, d.sphere_link + d.n_spheres, md.link);
     thip::lowering::store_sphere_groups(thip::lowering::group_spheres_by_link(d), md);
     for (int g = 0; g < md.n_groups; ++g)
       for (int k = md.grp_s0[g]; k < md.grp_s0[g] + md.grp_ns[g]; ++k)
         md.slot_grp[k] = g;
     md.n_self_keys = static_cast<int>(skp.size()) - 1;
-    md.n_self_sph = static_cast<int>(ssa.size());
     for (size_t k = 0; k < skp.size(); ++k)
       md.self_kp[k] = skp[k];
     for (int k = 0; k < md.n_self_keys; ++k)
       for (int j = skp[static_cast<size_t>(k)]; j < skp[static_cast<size_t>(k) + 1]; ++j)
-      {
-        md.self_sa[j] = ssa[static_cast<size_t>(j)];
-        md.self_sb[j] = ssb[static_cast<size_t>(j)];
         md.self_key[j] = k;
-      }
-    for (int s = 0; s < d.n_spheres; ++s)
-    {
-      md.link[s] = d.sphere_link[s];
-      md.radius[s] = d.sphere_radius[s];
-      for (int i = 0; i < 3; ++i)
-        md.center[s][i] = d.sphere_center[s][i];
-    }
   }
-  auto hfail = [&](const char* what, hipError_t e) {
-    g_check_create_err = std::string("thip_check_create: ") + what + ": " + hipGetErrorString(e);
-    thip_check_destroy(c);
-    return THIP_E_HIP;
-  };
   hipError_t e;
   if ((e = hipSetDevice(device)) != hipSuccess)
-    return hfail("hipSetDevice", e);
+    return reject.hip("hipSetDevice", e);
   const size_t B = static_cast<size_t>(batch), nu = static_cast<size_t>(n_units);
   const size_t np = static_cast<size_t>(std::max(desc->n_prims, 1));
-  if ((e = hipMalloc(&c->d_chain, sizeof(thip_chain))) != hipSuccess ||
-      (e = hipMalloc(&c->d_model, sizeof(Model))) != hipSuccess ||
-      (e = hipMalloc(&c->d_scene, B * np * 16 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_x, B * static_cast<size_t>(N) * c->D * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_recs, B * nu * sizeof(UnitRec))) != hipSuccess ||
-      (e = hipMalloc(&c->d_unit_min, B * nu * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&c->d_results, B * sizeof(thip_check_result))) != hipSuccess)
-    return hfail("hipMalloc", e);
-  if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
-    return hfail("hipStreamCreate", e);
-  if ((e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess)
-    return hfail("hipEventCreate", e);
+  if ((e = alloc(*c, c->d_chain, 1)) != hipSuccess || (e = alloc(*c, c->d_model, 1)) != hipSuccess ||
+      (e = alloc(*c, c->d_scene, B * np * 16)) != hipSuccess ||
+      (e = alloc(*c, c->d_x, B * static_cast<size_t>(N) * c->D)) != hipSuccess ||
+      (e = alloc(*c, c->d_recs, B * nu)) != hipSuccess || (e = alloc(*c, c->d_unit_min, B * nu)) != hipSuccess ||
+      (e = alloc(*c, c->d_results, B)) != hipSuccess)
+    return reject.hip("hipMalloc", e);
+  if ((e = open_stream(*c)) != hipSuccess)
+    return reject.hip("hipStreamCreate", e);
+  if ((e = open_events(*c)) != hipSuccess)
+    return reject.hip("hipEventCreate", e);
   // results are written field by field: clear once so the padding bytes are the same every run
   if ((e = hipMemcpyAsync(c->d_chain, &chain, sizeof(thip_chain), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
       (e = hipMemcpyAsync(c->d_model, &md, sizeof(Model), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
@@ -570,72 +534,34 @@ int thip_check_create(int device, const thip_problem_desc* desc, const thip_chec
       (e = hipMemsetAsync(c->d_recs, 0, B * nu * sizeof(UnitRec), c->stream)) != hipSuccess ||
       (e = hipMemsetAsync(c->d_results, 0, B * sizeof(thip_check_result), c->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-    return hfail("hipMemcpy", e);
-  *out = c;
-  return THIP_OK;
-}
-
-static int upload_scene(thip_check* c, const double* scene, hipMemcpyKind kind, const char* who)
-{
-  if (!c)
-    return THIP_E_INVALID;
-  if (c->pr.n_prims > 0 && !scene)
-    return cfail(c, std::string(who) + ": scene required when n_prims > 0");
-  hipError_t e;
-  if ((e = hipSetDevice(c->device)) != hipSuccess)
-    return chipfail(c, "hipSetDevice", e);
-  if (c->pr.n_prims > 0 &&
-      ((e = hipMemcpyAsync(c->d_scene, scene,
-                           static_cast<size_t>(c->batch) * static_cast<size_t>(c->pr.n_prims) * 16 * sizeof(double), kind,
-                           c->stream)) != hipSuccess ||
-       (e = hipStreamSynchronize(c->stream)) != hipSuccess))
-    return chipfail(c, "hipMemcpy(scene)", e);
-  c->uploaded = true;
+    return reject.hip("hipMemcpy", e);
+  *out = c.release();
   return THIP_OK;
 }
 
 int thip_check_upload(thip_check* chk, const double* scene)
 {
-  return upload_scene(chk, scene, hipMemcpyHostToDevice, "thip_check_upload");
+  return chk ? upload_scene(chk, chk->d_scene, chk->pr.n_prims, scene, hipMemcpyHostToDevice, "thip_check_upload")
+             : THIP_E_INVALID;
 }
 
 int thip_check_upload_device(thip_check* chk, const double* d_scene)
 {
-  return upload_scene(chk, d_scene, hipMemcpyDeviceToDevice, "thip_check_upload_device");
+  return chk ? upload_scene(chk, chk->d_scene, chk->pr.n_prims, d_scene, hipMemcpyDeviceToDevice,
+                            "thip_check_upload_device")
+             : THIP_E_INVALID;
 }
 
 int thip_check_units(const thip_check* chk) { return chk ? chk->pr.n_units : THIP_E_INVALID; }
 
 int thip_check_run(thip_check* chk, const double* x, thip_check_result* results, double* unit_min)
 {
-  if (!chk)
-    return THIP_E_INVALID;
-  if (!x || !results)
-    return cfail(chk, "thip_check_run: null x / results");
-  if (!chk->uploaded)
-    return cfail(chk, "thip_check_run: thip_check_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(chk->device)) != hipSuccess)
-    return chipfail(chk, "hipSetDevice", e);
-  if ((e = hipMemcpyAsync(chk->d_x, x,
-                          static_cast<size_t>(chk->batch) * static_cast<size_t>(chk->pr.N) * chk->D * sizeof(double),
-                          hipMemcpyHostToDevice, chk->stream)) != hipSuccess)
-    return chipfail(chk, "hipMemcpy(x)", e);
-  return run_on_device(chk, chk->d_x, results, unit_min);
+  return run(chk, true, x, results, unit_min);
 }
 
 int thip_check_run_device(thip_check* chk, const double* d_x, thip_check_result* results, double* unit_min)
 {
-  if (!chk)
-    return THIP_E_INVALID;
-  if (!d_x || !results)
-    return cfail(chk, "thip_check_run_device: null d_x / results");
-  if (!chk->uploaded)
-    return cfail(chk, "thip_check_run_device: thip_check_upload first");
-  hipError_t e;
-  if ((e = hipSetDevice(chk->device)) != hipSuccess)
-    return chipfail(chk, "hipSetDevice", e);
-  return run_on_device(chk, d_x, results, unit_min);
+  return run(chk, false, d_x, results, unit_min);
 }
 
 double thip_check_last_ms(thip_check* chk) { return chk ? chk->last_ms : -1.0; }
@@ -644,22 +570,7 @@ void thip_check_destroy(thip_check* chk)
 {
   if (!chk)
     return;
-  hipSetDevice(chk->device);
-  if (chk->stream)
-    hipStreamSynchronize(chk->stream);
-  hipFree(chk->d_chain);
-  hipFree(chk->d_model);
-  hipFree(chk->d_scene);
-  hipFree(chk->d_x);
-  hipFree(chk->d_recs);
-  hipFree(chk->d_unit_min);
-  hipFree(chk->d_results);
-  if (chk->ev0)
-    hipEventDestroy(chk->ev0);
-  if (chk->ev1)
-    hipEventDestroy(chk->ev1);
-  if (chk->stream)
-    hipStreamDestroy(chk->stream);
+  release(*chk);
   delete chk;
 }
 
