@@ -951,6 +951,46 @@ int thip_qp_warm_start(thip_qp* qp, const double* x, const double* y);
 /* osqp_solve from the kept iterates (warm_starting) or from zero: x [batch][n], y [batch][m] (may be NULL) */
 int thip_qp_solve_resident(thip_qp* qp, double* x, double* y, thip_qp_info* info);
 
+/* A masked, fused step on the resident workspaces: one launch, workgroup b runs
+ * the operations set in ops[b] on workspace b, in the order of the bits below
+ * (the order TrustRegionSQPSolver::stepSQPSolver issues them through a
+ * QPSolver), so the QPs of many lock-step SQP loops advance together although
+ * one re-convexifies, one only moved its trust box and one is finished.
+ *
+ * For every QP the workspace, x, y and info after a step are bit for bit what
+ * these calls give on a batch-1 object with the same data:
+ *   SETUP       thip_qp_setup                (needs P, q, A, l, u; excludes the four updates)
+ *   MAT_P       thip_qp_update_mat(P, NULL)
+ *   VEC_Q       thip_qp_update_vec(q, NULL, NULL)
+ *   MAT_A       thip_qp_update_mat(NULL, A)
+ *   VEC_BOUNDS  thip_qp_update_vec(NULL, l, u)
+ *   WARM        thip_qp_warm_start(warm_x, warm_y)   (warm starting stays on for this QP)
+ *   SOLVE       thip_qp_solve_resident
+ * Arrays are [batch][...]; the rows of QPs whose ops do not use them are ignored,
+ * and a pointer may be NULL when no QP uses it.  ops[b] == 0: workspace b is not
+ * touched and row b of x, y and info is left as the caller passed it (info is
+ * not written by WARM alone either, as thip_qp_warm_start takes none).
+ *
+ * State is per QP.  A QP is live after a SETUP whose info.status is not -1, and
+ * stops being live when a refactorisation fails (setup_error 4 / 5).  l <= u is
+ * checked per QP before the launch: an offending QP gets status -1,
+ * setup_error 1 and all its ops of this step are dropped (on an update its
+ * workspace keeps its data and stays live); the other QPs proceed.  A QP
+ * selected without SETUP that is not live: THIP_E_STATE, nothing is launched
+ * or changed, thip_qp_last_error names the QP.  settings are read when a QP
+ * has SETUP (may be NULL otherwise) and hold for the whole object: a SETUP with
+ * settings that differ from those of another live QP is THIP_E_INVALID.
+ *
+ * The whole-batch calls above keep their own state: thip_qp_setup makes every
+ * QP live for thip_qp_step as well; a thip_qp_step SETUP does not make the
+ * object resident for them.  (Added functions do not change THIP_ABI_VERSION:
+ * no struct changes layout.) */
+enum { THIP_QP_OP_SETUP = 1, THIP_QP_OP_MAT_P = 2, THIP_QP_OP_VEC_Q = 4, THIP_QP_OP_MAT_A = 8,
+       THIP_QP_OP_VEC_BOUNDS = 16, THIP_QP_OP_WARM = 32, THIP_QP_OP_SOLVE = 64 };
+int thip_qp_step(thip_qp* qp, const int* ops /*[batch]*/, const double* P_values, const double* q,
+                 const double* A_values, const double* l, const double* u, const thip_osqp_settings* settings,
+                 const double* warm_x, const double* warm_y, double* x, double* y, thip_qp_info* info);
+
 /* ------------------------------------------------------- Collision sets
  * The rows of trajopt_ifopt's fixed-size DiscreteCollisionConstraint over a
  * SingleTimestepCollisionEvaluator (trajopt_ifopt/src/constraints/collision/

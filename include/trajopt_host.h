@@ -304,6 +304,34 @@ int thost_tsqp_sizeof_cart_term(void);
 int thost_tsqp_sizeof_coll_term(void);
 int thost_tsqp_sizeof_ccoll_term(void);
 
+/* A batch of trajopt_sqp problems in lock step on one device
+ * (trajopt_sqp::BatchTrustRegionSQPSolver): every problem runs the
+ * TrustRegionSQPSolver of thost_tsqp_solve / thost_tsqp_solve_kin on a host
+ * thread of its own, and the QPs of a round run as one thip_qp_step per group
+ * of problems that share a QP pattern, sizes and OSQP settings.  Every
+ * problem's x and result are bit for bit those of its solve alone.
+ *   specs [batch], kins [batch] (NULL: joint terms only)
+ *   x [batch][TSQP_MAX_NODES * THIP_MAX_DOF]: problem b's [n_nodes][n_dof] at x + b * that stride
+ *   results [batch]; qp_rounds [batch] (may be NULL): the rounds problem b took part in
+ *   stats (may be NULL)
+ * batch < 1 or a NULL specs / x / results is an error before any device call.
+ * When problems fail, the others still finish: the return value is -1, err
+ * holds "problem <b>: <message>" of each failed problem (one per line), and a
+ * failed problem's result has status -1. */
+typedef struct tsqp_batch_stats {
+  long long rounds;          /* rendezvous rounds */
+  long long step_launches;   /* thip_qp_step launches: one per group with a waiting problem, per round */
+  long long groups;          /* thip_qp objects created: one symbolic KKT analysis each */
+  long long max_group;       /* the largest batch of one */
+  long long set_launches[2]; /* launches of the problems' CartPos evaluators and collision evaluators (each problem's
+                                sets launch for their own problem), as thost_tsqp_eval_kin counts them */
+} tsqp_batch_stats;
+int thost_tsqp_solve_batch(const tsqp_spec* specs, const tsqp_kin_spec* kins /* NULL: joint terms only */, int batch,
+                           int device, double* x /* [batch][TSQP_MAX_NODES*THIP_MAX_DOF] stride */,
+                           tsqp_result* results, int* qp_rounds /*[batch]*/, tsqp_batch_stats* stats, char* err,
+                           int err_len);
+int thost_tsqp_sizeof_batch_stats(void);
+
 #ifdef __cplusplus
 }
 #endif

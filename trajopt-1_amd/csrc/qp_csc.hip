@@ -1418,18 +1418,25 @@ __device__ void report_setup_error(Qp& q, thip_qp_info* info, int code)
   }
 }
 
-__global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
+// The inputs one resident operation reads ([batch][...], null = not given).
+struct ResIn
 {
-  extern __shared__ double lv[];
-  __shared__ Sh sh;
-  const int b = blockIdx.x;
-  if (b >= args.batch)
-    return;
+  const double *Pv, *qv, *Av, *lv, *uv, *x_ws, *y_ws;
+};
+
+// One resident operation on workspace b, by every thread of its workgroup:
+// the whole body of a qp_resident_kernel launch, so that qp_step_kernel runs
+// the same code for each of its operations.  lds: the dynamic LDS (fac_views
+// stages the kept factor from W_LX / W_DG, as a launch of its own would).
+// warm: settings.warm_starting of this QP.  False when the workspace is gone
+// (a refactorisation failed, or a solve found it so).
+__device__ __forceinline__ bool resident_op(Qp& q, const QpArgs& args, const ResIn& in, int b, int op, bool warm,
+                                            char* lds)
+{
+  Sh& sh = q.sh;
   const QpPattern& P = args.pat;
   const int n = P.n, m = P.m;
-  double* w = args.ws + (long long)b * P.stride;
-  Qp q{ P, args.s, w, sh, P.lds_vec ? lv : w + P.off[W_LV], n, m, {}, {}, true };
-  fac_views(q, reinterpret_cast<char*>(lv));
+  fac_views(q, lds);
   double* SC = q.a(W_SC);
   thip_qp_info* info = args.info + b;
   const bool sc = args.s.scaling > 0;
@@ -1453,13 +1460,13 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
   int err = 0;
   if (op == OP_SETUP)
   {
-    QFOR(e, P.nnz_p) PX[e] = args.Pv[(long long)b * P.nnz_p + e];
-    QFOR(e, P.nnz_a) AX[e] = args.Av[(long long)b * P.nnz_a + e];
-    QFOR(j, n) Q[j] = args.qv[(long long)b * n + j];
+    QFOR(e, P.nnz_p) PX[e] = in.Pv[(long long)b * P.nnz_p + e];
+    QFOR(e, P.nnz_a) AX[e] = in.Av[(long long)b * P.nnz_a + e];
+    QFOR(j, n) Q[j] = in.qv[(long long)b * n + j];
     QFOR(r, m)
     {
-      L[r] = args.lv[(long long)b * m + r];
-      U[r] = args.uv[(long long)b * m + r];
+      L[r] = in.lv[(long long)b * m + r];
+      U[r] = in.uv[(long long)b * m + r];
     }
     __syncthreads();
     if (sc)
@@ -1480,14 +1487,14 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
   }
   else if (op == OP_UPDATE_VEC)
   {
-    if (args.qv)
-      QFOR(j, n) Q[j] = sc ? (D[j] * args.qv[(long long)b * n + j]) * sh.c : args.qv[(long long)b * n + j];
-    if (args.lv)
+    if (in.qv)
+      QFOR(j, n) Q[j] = sc ? (D[j] * in.qv[(long long)b * n + j]) * sh.c : in.qv[(long long)b * n + j];
+    if (in.lv)
     {
       QFOR(r, m)
       {
-        L[r] = sc ? E[r] * args.lv[(long long)b * m + r] : args.lv[(long long)b * m + r];
-        U[r] = sc ? E[r] * args.uv[(long long)b * m + r] : args.uv[(long long)b * m + r];
+        L[r] = sc ? E[r] * in.lv[(long long)b * m + r] : in.lv[(long long)b * m + r];
+        U[r] = sc ? E[r] * in.uv[(long long)b * m + r] : in.uv[(long long)b * m + r];
       }
       __syncthreads();
       // update_rho_vec: rows whose constraint type changed get their rho; a
@@ -1534,10 +1541,10 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
   {
     if (sc)
       unscale_data(q);
-    if (args.Pv)
-      QFOR(e, P.nnz_p) PX[e] = args.Pv[(long long)b * P.nnz_p + e];
-    if (args.Av)
-      QFOR(e, P.nnz_a) AX[e] = args.Av[(long long)b * P.nnz_a + e];
+    if (in.Pv)
+      QFOR(e, P.nnz_p) PX[e] = in.Pv[(long long)b * P.nnz_p + e];
+    if (in.Av)
+      QFOR(e, P.nnz_a) AX[e] = in.Av[(long long)b * P.nnz_a + e];
     __syncthreads();
     if (sc)
       scale_data(q);
@@ -1550,21 +1557,21 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
   else if (op == OP_WARM_START)
   {
     const double *DI = q.a(W_DI), *EI = q.a(W_EI);
-    if (args.x_ws)
+    if (in.x_ws)
     {
-      QFOR(j, n) X[j] = sc ? args.x_ws[(long long)b * n + j] * DI[j] : args.x_ws[(long long)b * n + j];
+      QFOR(j, n) X[j] = sc ? in.x_ws[(long long)b * n + j] * DI[j] : in.x_ws[(long long)b * n + j];
       __syncthreads();
       a_mul(q, X, Z);
     }
-    if (args.y_ws)
-      QFOR(r, m) Y[r] = sc ? (args.y_ws[(long long)b * m + r] * EI[r]) * sh.c : args.y_ws[(long long)b * m + r];
+    if (in.y_ws)
+      QFOR(r, m) Y[r] = sc ? (in.y_ws[(long long)b * m + r] * EI[r]) * sh.c : in.y_ws[(long long)b * m + r];
   }
   else  // OP_SOLVE
   {
     if (SC[SC_OK] == 0.0)
     {
       report_setup_error(q, info, 4);
-      return;
+      return false;
     }
     if (SC[SC_KKT_DIRTY] != 0.0)
     {
@@ -1572,7 +1579,7 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
       if (threadIdx.x == 0)
         SC[SC_KKT_DIRTY] = 0.0;
     }
-    if (!args.s.warm_starting)
+    if (!warm)
     {
       QFOR(j, n) X[j] = 0.0;
       QFOR(r, m) Z[r] = Y[r] = 0.0;
@@ -1585,7 +1592,7 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
         SC[SC_KKT_DIRTY] = 1.0;  // polish factored its KKT over W_LX / W_DG
       SC[SC_RHO] = sh.rho;
     }
-    return;
+    return true;
   }
   __syncthreads();
   if (!ok)
@@ -1608,6 +1615,78 @@ __global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
     SC[SC_C] = sh.c;
     SC[SC_CINV] = sh.cinv;
     SC[SC_RHO] = sh.rho;
+  }  return ok;
+}
+
+__global__ __launch_bounds__(kQB) void qp_resident_kernel(QpArgs args, int op)
+{
+  extern __shared__ double lv[];
+  __shared__ Sh sh;
+  const int b = blockIdx.x;
+  if (b >= args.batch)
+    return;
+  const QpPattern& P = args.pat;
+  double* w = args.ws + (long long)b * P.stride;
+  Qp q{ P, args.s, w, sh, P.lds_vec ? lv : w + P.off[W_LV], P.n, P.m, {}, {}, true };
+  const ResIn in{ args.Pv, args.qv, args.Av, args.lv, args.uv, args.x_ws, args.y_ws };
+  resident_op(q, args, in, b, op, args.s.warm_starting != 0, reinterpret_cast<char*>(lv));
+}
+
+// thip_qp_step: workgroup b runs the operations set in ops[b] on workspace b,
+// in the order of the THIP_QP_OP_* bits (the order TrustRegionSQPSolver::
+// stepSQPSolver issues them), each as the launch of its own would.  ops[b] is
+// one value per workgroup, so every barrier below is uniform.  kStepWarmOn (set
+// by the host, not by the caller): warm_starting of this QP.
+constexpr int kStepWarmOn = 1 << 16;
+__global__ __launch_bounds__(kQB) void qp_step_kernel(QpArgs args, const int* ops)
+{
+  extern __shared__ double lv[];
+  __shared__ Sh sh;
+  const int b = blockIdx.x;
+  if (b >= args.batch)
+    return;
+  const int mask = ops[b];
+  if ((mask & (THIP_QP_OP_SOLVE * 2 - 1)) == 0)
+    return;  // not selected: workspace b, x, y and info[b] untouched
+  const QpPattern& P = args.pat;
+  double* w = args.ws + (long long)b * P.stride;
+  Qp q{ P, args.s, w, sh, P.lds_vec ? lv : w + P.off[W_LV], P.n, P.m, {}, {}, true };
+  const bool warm = (mask & kStepWarmOn) != 0;
+  for (int bit = THIP_QP_OP_SETUP; bit <= THIP_QP_OP_SOLVE; bit <<= 1)
+  {
+    if (!(mask & bit))
+      continue;
+    ResIn in{};
+    int op = OP_SOLVE;
+    if (bit == THIP_QP_OP_SETUP)
+    {
+      op = OP_SETUP;
+      in = ResIn{ args.Pv, args.qv, args.Av, args.lv, args.uv, nullptr, nullptr };
+    }
+    else if (bit == THIP_QP_OP_MAT_P || bit == THIP_QP_OP_MAT_A)
+    {
+      op = OP_UPDATE_MAT;
+      in.Pv = bit == THIP_QP_OP_MAT_P ? args.Pv : nullptr;
+      in.Av = bit == THIP_QP_OP_MAT_A ? args.Av : nullptr;
+    }
+    else if (bit == THIP_QP_OP_VEC_Q || bit == THIP_QP_OP_VEC_BOUNDS)
+    {
+      op = OP_UPDATE_VEC;
+      in.qv = bit == THIP_QP_OP_VEC_Q ? args.qv : nullptr;
+      in.lv = bit == THIP_QP_OP_VEC_BOUNDS ? args.lv : nullptr;
+      in.uv = bit == THIP_QP_OP_VEC_BOUNDS ? args.uv : nullptr;
+    }
+    else if (bit == THIP_QP_OP_WARM)
+    {
+      op = OP_WARM_START;
+      in.x_ws = args.x_ws;
+      in.y_ws = args.y_ws;
+    }
+    const bool alive = resident_op(q, args, in, b, op, warm, reinterpret_cast<char*>(lv));
+    // the next operation restages LDS and thread 0 rewrites sh: every thread is done with both
+    __syncthreads();
+    if (!alive)
+      break;  // sh.fail / SC_OK: the same for every thread
   }
 }
 
@@ -1641,6 +1720,14 @@ struct thip_qp : thip::host::Handle  // stream: thip_qp_submit / thip_qp_collect
   // resident workspace (thip_qp_setup ...): the settings of its setup
   thip_osqp_settings rs{};
   bool resident = false;
+  // thip_qp_step: per-QP state (live workspace; warm starting on) over the
+  // settings of the last setup, the ops as launched, and the results' staging
+  thip_osqp_settings rs0{};
+  std::vector<char> alive, warm;
+  int* d_ops = nullptr;
+  std::vector<int> h_ops;
+  std::vector<double> h_xy;
+  std::vector<thip_qp_info> h_info;
 };
 
 static thread_local std::string g_qp_create_err;
@@ -1951,6 +2038,7 @@ static int qp_stage(thip_qp* q, int count, const double* P_values, const double*
     return THIP_E_HIP;
   }
   q->resident = false;  // the one-shot solve reuses the workspace
+  q->alive.assign(q->batch, 0);
   QpArgs a{};
   a.pat = q->pat;
   a.s = *settings;
@@ -2268,8 +2356,10 @@ int thip_qp_setup(thip_qp* q, const double* P_values, const double* qvec, const 
     q->err = "thip_qp_setup: " + q->err;
     return THIP_E_INVALID;
   }
-  q->rs = *settings;
+  q->rs = q->rs0 = *settings;
   q->resident = true;
+  q->alive.assign(q->batch, 0);  // thip_qp_step's view: live per QP where the setup succeeds
+  q->warm.assign(q->batch, settings->warm_starting != 0);
   if (q->m && !bounds_ok(q, l, u))
   {
     // OSQP_DATA_VALIDATION_ERROR: no workspace
@@ -2280,8 +2370,11 @@ int thip_qp_setup(thip_qp* q, const double* P_values, const double* qvec, const 
   const int rc = qp_resident(q, OP_SETUP, P_values, qvec, A_values, l, u, nullptr, nullptr, nullptr, nullptr, info);
   if (rc == THIP_OK)
     for (int b = 0; b < q->batch; ++b)
+    {
+      q->alive[b] = info[b].status != -1;
       if (info[b].status == -1)
         q->resident = false;
+    }
   return rc;
 }
 
@@ -2327,7 +2420,10 @@ int thip_qp_update_mat(thip_qp* q, const double* P_values, const double* A_value
   if (rc == THIP_OK)
     for (int b = 0; b < q->batch; ++b)
       if (info[b].status == -1)
+      {
         q->resident = false;
+        q->alive[b] = 0;
+      }
   return rc;
 }
 
@@ -2341,6 +2437,7 @@ int thip_qp_warm_start(thip_qp* q, const double* x, const double* y)
     return THIP_E_STATE;
   }
   q->rs.warm_starting = 1;  // osqp_warm_start turns warm starting on
+  q->warm.assign(q->batch, 1);
   return qp_resident(q, OP_WARM_START, nullptr, nullptr, nullptr, nullptr, nullptr, x, q->m ? y : nullptr, nullptr,
                      nullptr, nullptr);
 }
@@ -2360,6 +2457,209 @@ int thip_qp_solve_resident(thip_qp* q, double* x, double* y, thip_qp_info* info)
     return THIP_E_INVALID;
   }
   return qp_resident(q, OP_SOLVE, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, x, y, info);
+}
+
+static bool same_settings(const thip_osqp_settings& a, const thip_osqp_settings& b)
+{
+  return a.rho == b.rho && a.sigma == b.sigma && a.alpha == b.alpha && a.scaling == b.scaling &&
+         a.adaptive_rho == b.adaptive_rho && a.adaptive_rho_interval == b.adaptive_rho_interval &&
+         a.adaptive_rho_tolerance == b.adaptive_rho_tolerance && a.max_iter == b.max_iter && a.eps_abs == b.eps_abs &&
+         a.eps_rel == b.eps_rel && a.eps_prim_inf == b.eps_prim_inf && a.eps_dual_inf == b.eps_dual_inf &&
+         a.check_termination == b.check_termination && a.warm_starting == b.warm_starting &&
+         a.polishing == b.polishing && a.delta == b.delta && a.polish_refine_iter == b.polish_refine_iter;
+}
+
+int thip_qp_step(thip_qp* q, const int* ops, const double* P_values, const double* qvec, const double* A_values,
+                 const double* l, const double* u, const thip_osqp_settings* settings, const double* warm_x,
+                 const double* warm_y, double* x, double* y, thip_qp_info* info)
+{
+  if (!q)
+    return THIP_E_INVALID;
+  const int n = q->n, m = q->m, B = q->batch;
+  constexpr int kAll = THIP_QP_OP_SOLVE * 2 - 1;
+  constexpr int kUpdates = THIP_QP_OP_MAT_P | THIP_QP_OP_VEC_Q | THIP_QP_OP_MAT_A | THIP_QP_OP_VEC_BOUNDS;
+  if (!ops)
+  {
+    q->err = "thip_qp_step: null ops";
+    return THIP_E_INVALID;
+  }
+  if (q->pending || q->staged)
+  {
+    q->err = "thip_qp_step: a submission is not collected (thip_qp_collect first)";
+    return THIP_E_INVALID;
+  }
+  if (static_cast<int>(q->alive.size()) != B)
+  {
+    q->alive.assign(B, 0);
+    q->warm.assign(B, 0);
+  }
+  // every refusal comes before any change of state
+  int asked = 0;
+  bool other_live = false;
+  for (int b = 0; b < B; ++b)
+  {
+    const int o = ops[b];
+    if (o & ~kAll)
+    {
+      q->err = "thip_qp_step: QP " + std::to_string(b) + ": unknown bits in ops";
+      return THIP_E_INVALID;
+    }
+    if ((o & THIP_QP_OP_SETUP) && (o & kUpdates))
+    {
+      q->err = "thip_qp_step: QP " + std::to_string(b) + ": THIP_QP_OP_SETUP excludes the update bits";
+      return THIP_E_INVALID;
+    }
+    if (o && !(o & THIP_QP_OP_SETUP) && !q->alive[b])
+    {
+      q->err = "thip_qp_step: QP " + std::to_string(b) + " is selected without THIP_QP_OP_SETUP and has no live workspace";
+      return THIP_E_STATE;
+    }
+    other_live = other_live || (q->alive[b] && !(o & THIP_QP_OP_SETUP));
+    asked |= o;
+  }
+  const bool needP = (asked & (THIP_QP_OP_SETUP | THIP_QP_OP_MAT_P)) && q->nnz_p;
+  const bool needA = (asked & (THIP_QP_OP_SETUP | THIP_QP_OP_MAT_A)) && q->nnz_a;
+  const bool needq = (asked & (THIP_QP_OP_SETUP | THIP_QP_OP_VEC_Q)) != 0;
+  const bool needb = (asked & (THIP_QP_OP_SETUP | THIP_QP_OP_VEC_BOUNDS)) && m;
+  if ((needP && !P_values) || (needA && !A_values) || (needq && !qvec) || (needb && (!l || !u)) ||
+      ((asked & THIP_QP_OP_SETUP) && !settings) || ((asked & THIP_QP_OP_SOLVE) && !x) ||
+      ((asked & ~THIP_QP_OP_WARM) && !info))
+  {
+    q->err = "thip_qp_step: null argument for an operation in ops";
+    return THIP_E_INVALID;
+  }
+  if (asked & THIP_QP_OP_SETUP)
+  {
+    if (!qp_settings_ok(q, settings))
+    {
+      q->err = "thip_qp_step: " + q->err;
+      return THIP_E_INVALID;
+    }
+    if (other_live && !same_settings(*settings, q->rs0))
+    {
+      q->err = "thip_qp_step: THIP_QP_OP_SETUP with settings that differ from the live QPs' (one set per object)";
+      return THIP_E_INVALID;
+    }
+    q->rs0 = *settings;
+  }
+  // per-QP validate_data: l <= u, else the QP's ops of this step are dropped
+  q->h_ops.assign(B, 0);
+  int run = 0;
+  for (int b = 0; b < B; ++b)
+  {
+    int o = ops[b];
+    if (!o)
+      continue;
+    if (needb && (o & (THIP_QP_OP_SETUP | THIP_QP_OP_VEC_BOUNDS)))
+    {
+      bool ok = true;
+      for (long long r = static_cast<long long>(b) * m; r < static_cast<long long>(b + 1) * m && ok; ++r)
+        ok = l[r] <= u[r];
+      if (!ok)
+      {
+        info[b] = thip_qp_info{};
+        info[b].status = -1;
+        info[b].setup_error = 1;
+        if (o & THIP_QP_OP_SETUP)
+          q->alive[b] = 0;  // OSQP_DATA_VALIDATION_ERROR: no workspace
+        continue;
+      }
+    }
+    if (o & THIP_QP_OP_SETUP)
+      q->warm[b] = settings->warm_starting != 0;
+    if (o & THIP_QP_OP_WARM)
+      q->warm[b] = 1;  // osqp_warm_start turns warm starting on
+    q->h_ops[b] = o | (q->warm[b] ? kStepWarmOn : 0);
+    run |= o;
+  }
+  if (!run)
+    return THIP_OK;
+  hipError_t e;
+  if ((e = hipSetDevice(q->device)) != hipSuccess)
+  {
+    q->err = std::string("hipSetDevice: ") + hipGetErrorString(e);
+    return THIP_E_HIP;
+  }
+  if (!q->d_ops && (e = alloc(*q, q->d_ops, static_cast<size_t>(B))) != hipSuccess)
+  {
+    q->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+    return THIP_E_HIP;
+  }
+  const size_t np = static_cast<size_t>(q->nnz_p) * B, na = static_cast<size_t>(q->nnz_a) * B;
+  const size_t nn = static_cast<size_t>(n) * B, mm = static_cast<size_t>(m) * B;
+  double* d = q->d_in;
+  double *dP = d, *dA = dP + np, *dq = dA + na, *dl = dq + nn, *du = dl + mm, *dxw = du + mm, *dyw = dxw + nn;
+  const bool useP = (run & (THIP_QP_OP_SETUP | THIP_QP_OP_MAT_P)) && np;
+  const bool useA = (run & (THIP_QP_OP_SETUP | THIP_QP_OP_MAT_A)) && na;
+  const bool useq = (run & (THIP_QP_OP_SETUP | THIP_QP_OP_VEC_Q)) != 0;
+  const bool useb = (run & (THIP_QP_OP_SETUP | THIP_QP_OP_VEC_BOUNDS)) && mm;
+  const bool usex = (run & THIP_QP_OP_WARM) && warm_x;
+  const bool usey = (run & THIP_QP_OP_WARM) && warm_y && mm;
+  auto h2d = [&](void* dst, const void* src, size_t bytes) {
+    return (e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)) == hipSuccess;
+  };
+  if ((useP && !h2d(dP, P_values, np * sizeof(double))) || (useA && !h2d(dA, A_values, na * sizeof(double))) ||
+      (useq && !h2d(dq, qvec, nn * sizeof(double))) ||
+      (useb && (!h2d(dl, l, mm * sizeof(double)) || !h2d(du, u, mm * sizeof(double)))) ||
+      (usex && !h2d(dxw, warm_x, nn * sizeof(double))) || (usey && !h2d(dyw, warm_y, mm * sizeof(double))) ||
+      !h2d(q->d_ops, q->h_ops.data(), static_cast<size_t>(B) * sizeof(int)))
+  {
+    q->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
+    return THIP_E_HIP;
+  }
+  QpArgs a{};
+  a.pat = q->pat;
+  a.s = q->rs0;
+  a.Pv = useP ? dP : nullptr;
+  a.Av = useA ? dA : nullptr;
+  a.qv = useq ? dq : nullptr;
+  a.lv = useb ? dl : nullptr;
+  a.uv = useb ? du : nullptr;
+  a.x_ws = usex ? dxw : nullptr;
+  a.y_ws = usey ? dyw : nullptr;
+  a.x_out = q->d_out;
+  a.y_out = q->d_out + nn;
+  a.info = q->d_info;
+  a.ws = q->d_ws;
+  a.batch = B;
+  // its own attribute: the one qp_resident sets names qp_resident_kernel only
+  if (q->lds > 65536)
+    hipFuncSetAttribute(reinterpret_cast<const void*>(&qp_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                        static_cast<int>(q->lds));
+  hipLaunchKernelGGL(qp_step_kernel, dim3(B), dim3(kQB), q->lds, nullptr, a, q->d_ops);
+  if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
+  {
+    q->err = std::string("qp_step_kernel: ") + hipGetErrorString(e);
+    return THIP_E_HIP;
+  }
+  q->h_info.resize(B);
+  q->h_xy.resize(nn + mm);
+  if (((run & THIP_QP_OP_SOLVE) &&
+       (e = hipMemcpy(q->h_xy.data(), q->d_out, (nn + mm) * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) ||
+      ((run & ~THIP_QP_OP_WARM) &&
+       (e = hipMemcpy(q->h_info.data(), q->d_info, sizeof(thip_qp_info) * B, hipMemcpyDeviceToHost)) != hipSuccess))
+  {
+    q->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
+    return THIP_E_HIP;
+  }
+  for (int b = 0; b < B; ++b)
+  {
+    const int o = q->h_ops[b] & kAll;
+    if (!(o & ~THIP_QP_OP_WARM))
+      continue;
+    info[b] = q->h_info[b];
+    if (info[b].status == -1)
+      q->alive[b] = 0;  // the refactorisation failed: the workspace is gone
+    else if (o & THIP_QP_OP_SETUP)
+      q->alive[b] = 1;
+    if (o & THIP_QP_OP_SOLVE)
+    {
+      std::copy_n(q->h_xy.data() + static_cast<size_t>(b) * n, n, x + static_cast<size_t>(b) * n);
+      if (y && m)
+        std::copy_n(q->h_xy.data() + nn + static_cast<size_t>(b) * m, m, y + static_cast<size_t>(b) * m);
+    }
+  }
+  return THIP_OK;
 }
 
 void thip_qp_destroy(thip_qp* q)

@@ -12,37 +12,24 @@
 #include <stdexcept>
 #include <string>
 
+#include "qp_data.h"
 #include "trajopt_sqp/qp_problem.h"
 
 namespace trajopt_sqp
 {
 namespace
 {
-constexpr double kOsqpInfty = 1e30;  // OSQP_INFTY
+using qp_data::kOsqpInfty;
 
-// CSC of a row-major matrix (all stored entries, zeros included), optionally the
-// upper triangle only, scaled
+// the conversions shared with GpuQPBatch::Slot (qp_data.h)
 void toCsc(const trajopt_ifopt::Jacobian& J, bool upper, double scale, std::vector<int>& p, std::vector<int>& idx,
            std::vector<double>& x)
 {
-  const long n = J.cols();
-  std::vector<std::vector<std::pair<int, double>>> col(static_cast<std::size_t>(n));
-  for (long r = 0; r < J.rows(); ++r)
-    for (long e = J.rowBegin(r); e < J.rowEnd(r); ++e)
-      if (!upper || r <= J.col(e))
-        col[static_cast<std::size_t>(J.col(e))].emplace_back(static_cast<int>(r), J.value(e) * scale);
-  p.assign(static_cast<std::size_t>(n) + 1, 0);
-  idx.clear();
-  x.clear();
-  for (long j = 0; j < n; ++j)
-  {
-    for (const auto& e : col[static_cast<std::size_t>(j)])  // rows ascending: row-major scan order
-    {
-      idx.push_back(e.first);
-      x.push_back(e.second);
-    }
-    p[static_cast<std::size_t>(j) + 1] = static_cast<int>(idx.size());
-  }
+  qp_data::Csc c;
+  qp_data::toCsc(J, upper, scale, c);
+  p = std::move(c.p);
+  idx = std::move(c.i);
+  x = std::move(c.x);
 }
 }  // namespace
 
@@ -146,9 +133,7 @@ bool GpuQPSolver::updateHessianMatrix(const trajopt_ifopt::Jacobian& hessian)
 
 bool GpuQPSolver::updateGradient(const trajopt_ifopt::VectorXd& gradient)
 {
-  q_.resize(gradient.size());
-  for (std::size_t j = 0; j < gradient.size(); ++j)
-    q_[j] = (std::abs(gradient[j]) < 1e-7) ? 0.0 : gradient[j];
+  qp_data::cleanGradient(gradient, q_);
   if (!resident_)
     return true;
   if (thip_qp_update_vec(qp_, q_.data(), nullptr, nullptr, &info_) != THIP_OK)
@@ -168,12 +153,7 @@ bool GpuQPSolver::updateUpperBound(const trajopt_ifopt::VectorXd& upperBound)
 
 bool GpuQPSolver::updateBounds(const trajopt_ifopt::VectorXd& lowerBound, const trajopt_ifopt::VectorXd& upperBound)
 {
-  lo_.resize(lowerBound.size());
-  up_.resize(upperBound.size());
-  for (std::size_t r = 0; r < lowerBound.size(); ++r)
-    lo_[r] = std::max(lowerBound[r], -kOsqpInfty);
-  for (std::size_t r = 0; r < upperBound.size(); ++r)
-    up_[r] = std::min(upperBound[r], kOsqpInfty);
+  qp_data::clampBounds(lowerBound, upperBound, lo_, up_);
   if (!resident_)
     return true;
   if (thip_qp_update_vec(qp_, nullptr, lo_.data(), up_.data(), &info_) != THIP_OK)
@@ -203,27 +183,12 @@ bool GpuQPSolver::updateLinearConstraintsMatrix(const trajopt_ifopt::Jacobian& l
   return info_.status != -1;
 }
 
-// osqp_eigen_solver.cpp:267-324: primal start = [NLP values; slacks], the slack
-// of constraint-matrix row k from convex violation k (the reference pairs the
-// k-th merit violation with the k-th matrix row), dual start 0
+// the stored warm start of the next setup (qp_data::warmStartPoint)
 bool GpuQPSolver::setWarmStart(const QPProblem& qp_problem)
 {
   if (settings.warm_starting != 1)
     return true;
-  const long nn = qp_problem.getNumNLPVars();
-  x0_.assign(static_cast<std::size_t>(nv_), 0.0);
-  const trajopt_ifopt::VectorXd vars = qp_problem.getVariableValues();
-  std::copy(vars.begin(), vars.begin() + nn, x0_.begin());
-  if (nv_ > nn)
-  {
-    const trajopt_ifopt::VectorXd viol = qp_problem.evaluateConvexConstraintViolations(vars);
-    const trajopt_ifopt::Jacobian& A = qp_problem.getConstraintMatrix();
-    for (long k = 0; k < static_cast<long>(viol.size()) && k < A.rows(); ++k)
-      for (long e = A.rowBegin(k); e < A.rowEnd(k); ++e)
-        if (A.col(e) >= nn && std::abs(A.value(e)) > 1e-14)
-          x0_[static_cast<std::size_t>(A.col(e))] = std::max(0.0, viol[static_cast<std::size_t>(k)] / A.value(e));
-  }
-  y0_.assign(static_cast<std::size_t>(nc_), 0.0);
+  qp_data::warmStartPoint(qp_problem, nv_, nc_, x0_, y0_);
   return true;
 }
 

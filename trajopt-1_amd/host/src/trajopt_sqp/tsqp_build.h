@@ -2,12 +2,14 @@
 // tsqp_kin_capi.cpp): a tsqp_spec as NodesVariables + joint constraint sets in a
 // TrajOptQPProblem, and the solve of a built problem.
 #pragma once
+#include <functional>
 #include <memory>
 #include <vector>
 
 #include "trajopt_host.h"
 #include "trajopt_ifopt/core/constraint_set.h"
 #include "trajopt_sqp/trajopt_qp_problem.h"
+#include "trajopt_sqp/types.h"
 
 namespace trajopt_sqp
 {
@@ -22,6 +24,18 @@ struct Built
 };
 // the spec's variables and joint terms (`who` prefixes the error messages)
 Built buildJointProblem(const tsqp_spec* spec, const char* who);
+// the spec's SQPParameters
+SQPParameters paramsOf(const tsqp_spec* spec);
+// the spec with the kinematic sets of `kin` added after its joint terms (tsqp_kin_capi.cpp).  `keep` owns the
+// environment and the device evaluators of the sets; set_launches: the launches of the CartPos evaluator [0] and of
+// the collision evaluators [1] so far, as thost_tsqp_eval_kin counts them.
+struct KinProblem
+{
+  Built joint;
+  std::shared_ptr<void> keep;
+  std::function<void(long long* out)> set_launches;
+};
+KinProblem buildKinProblem(const tsqp_spec* spec, const tsqp_kin_spec* kin, int device, const char* who);
 // setup + TrustRegionSQPSolver over a GpuQPSolver with the spec's parameters: x [n_nodes][n_dof], result may be null
 void solveBuilt(Built& b, const tsqp_spec* spec, int device, const char* who, double* x, tsqp_result* result);
 }  // namespace capi

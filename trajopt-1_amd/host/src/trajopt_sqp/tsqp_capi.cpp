@@ -112,21 +112,9 @@ Built buildJointProblem(const tsqp_spec* s, const char* who)
   return out;
 }
 
-void solveBuilt(Built& b, const tsqp_spec* s, int device, const char* who, double* x, tsqp_result* result)
+trajopt_sqp::SQPParameters paramsOf(const tsqp_spec* s)
 {
-  const std::string w(who);
-  auto& problem = b.problem;
-  problem->setup();
-  // the QP keeps one size for the whole solve: check the GPU solver's capacity up front
-  if (problem->getNumQPVars() + problem->getNumQPConstraints() > THIP_QP_MAX_KKT)
-    throw std::runtime_error(w + ": the QP has " + std::to_string(problem->getNumQPVars()) +
-                             " variables and " + std::to_string(problem->getNumQPConstraints()) +
-                             " constraints; the GPU QP solver takes n + m <= THIP_QP_MAX_KKT (" +
-                             std::to_string(THIP_QP_MAX_KKT) + ")");
-  auto qp_solver = std::make_shared<trajopt_sqp::GpuQPSolver>(device);
-  qp_solver->settings = s->osqp;
-  trajopt_sqp::TrustRegionSQPSolver solver(qp_solver);
-  trajopt_sqp::SQPParameters& p = solver.params;
+  trajopt_sqp::SQPParameters p;
   p.improve_ratio_threshold = s->improve_ratio_threshold;
   p.min_trust_box_size = s->min_trust_box_size;
   p.min_approx_improve = s->min_approx_improve;
@@ -142,6 +130,24 @@ void solveBuilt(Built& b, const tsqp_spec* s, int device, const char* who, doubl
   p.initial_merit_error_coeff = s->initial_merit_error_coeff;
   p.inflate_constraints_individually = s->inflate_constraints_individually != 0;
   p.initial_trust_box_size = s->initial_trust_box_size;
+  return p;
+}
+
+void solveBuilt(Built& b, const tsqp_spec* s, int device, const char* who, double* x, tsqp_result* result)
+{
+  const std::string w(who);
+  auto& problem = b.problem;
+  problem->setup();
+  // the QP keeps one size for the whole solve: check the GPU solver's capacity up front
+  if (problem->getNumQPVars() + problem->getNumQPConstraints() > THIP_QP_MAX_KKT)
+    throw std::runtime_error(w + ": the QP has " + std::to_string(problem->getNumQPVars()) +
+                             " variables and " + std::to_string(problem->getNumQPConstraints()) +
+                             " constraints; the GPU QP solver takes n + m <= THIP_QP_MAX_KKT (" +
+                             std::to_string(THIP_QP_MAX_KKT) + ")");
+  auto qp_solver = std::make_shared<trajopt_sqp::GpuQPSolver>(device);
+  qp_solver->settings = s->osqp;
+  trajopt_sqp::TrustRegionSQPSolver solver(qp_solver);
+  solver.params = paramsOf(s);
   solver.solve(problem);
   const VectorXd xv = problem->getVariableValues();
   std::memcpy(x, xv.data(), sizeof(double) * xv.size());

@@ -160,7 +160,33 @@ KinBuilt buildKin(const tsqp_spec* s, const tsqp_kin_spec* k, int device, const 
   }
   return out;
 }
+
+void setLaunches(const KinBuilt& b, long long* launches)
+{
+  launches[0] = b.cart_eval ? b.cart_eval->launches() : 0;
+  launches[1] = 0;
+  for (const auto& ev : b.coll_evals)
+    launches[1] += ev->launches();
+  for (const auto& ev : b.ccoll_evals)
+    launches[1] += ev->launches();
+}
 }  // namespace
+
+namespace trajopt_sqp
+{
+namespace capi
+{
+KinProblem buildKinProblem(const tsqp_spec* spec, const tsqp_kin_spec* kin, int device, const char* who)
+{
+  auto kb = std::make_shared<KinBuilt>(buildKin(spec, kin, device, who));
+  KinProblem out;
+  out.joint = kb->joint;
+  out.keep = kb;
+  out.set_launches = [kb](long long* launches) { setLaunches(*kb, launches); };
+  return out;
+}
+}  // namespace capi
+}  // namespace trajopt_sqp
 
 extern "C" {
 
@@ -259,14 +285,7 @@ int thost_tsqp_eval_kin(const tsqp_spec* s, const tsqp_kin_spec* k, int device, 
       }
     }
     if (launches)
-    {
-      launches[0] = b.cart_eval ? b.cart_eval->launches() : 0;
-      launches[1] = 0;
-      for (const auto& ev : b.coll_evals)
-        launches[1] += ev->launches();
-      for (const auto& ev : b.ccoll_evals)
-        launches[1] += ev->launches();
-    }
+      setLaunches(b, launches);
     return 0;
   }
   catch (const std::exception& e)

@@ -352,6 +352,11 @@ class TermSlot(C.Structure):
     ]
 
 
+# thip_qp_step's per-QP operation bits (THIP_QP_OP_*), run in this order
+QP_OP_SETUP, QP_OP_MAT_P, QP_OP_VEC_Q, QP_OP_MAT_A, QP_OP_VEC_BOUNDS, QP_OP_WARM, QP_OP_SOLVE = 1, 2, 4, 8, 16, 32, 64
+E_INVALID, E_HIP, E_NOMEM, E_STATE = -1, -2, -3, -4  # THIP_E_*
+
+
 class QpInfo(C.Structure):
     """thip_qp_info (include/trajopt_hip.h): one generic QP's solve report."""
 
@@ -632,6 +637,9 @@ def _declare(lib):
     lib.thip_qp_warm_start.restype = C.c_int
     lib.thip_qp_solve_resident.argtypes = [vp, dp, dp, qi]
     lib.thip_qp_solve_resident.restype = C.c_int
+    # ops [batch] of QP_OP_* bits; P, q, A, l, u; settings; warm x, y; out x, y, info
+    lib.thip_qp_step.argtypes = [vp, ip, dp, dp, dp, dp, dp, sp, dp, dp, dp, dp, qi]
+    lib.thip_qp_step.restype = C.c_int
     lib.thip_sizeof_desc.argtypes = []
     lib.thip_sizeof_desc.restype = C.c_int
     lib.thip_sizeof_result.argtypes = []

@@ -7,6 +7,9 @@ the QP lives in thip_qp's resident GPU workspace (trajopt_sqp::GpuQPSolver).
 `Spec` mirrors tsqp_spec: a joint trajectory of n_nodes nodes with joint
 position / velocity / acceleration / jerk terms, as constraints or as squared /
 absolute / hinge costs.  `solve` runs the C++ product path on a HIP device.
+`solve_batch` runs many problems in lock step on one device
+(trajopt_sqp::BatchTrustRegionSQPSolver: one thip_qp_step launch per round and QP
+pattern), every problem's result bit for bit the one of its solve alone.
 `KinSpec` mirrors tsqp_kin_spec: CartPosConstraint sets and fixed-size
 DiscreteCollisionConstraint sets on the built-in environment of a group, their
 values and jacobians from the device; `solve_kin` solves with them, `eval_kin`
@@ -87,10 +90,23 @@ class KinSpec(C.Structure):
                 ("n_ccoll", C.c_int), ("ccoll", CcollTerm * KIN_MAX_COLL)]
 
 
+class BatchStats(C.Structure):
+    """tsqp_batch_stats: rendezvous rounds, thip_qp_step launches, thip_qp objects created (one symbolic analysis
+    each), the largest of them, and the launches of the problems' CartPos / collision evaluators."""
+    _fields_ = [("rounds", C.c_longlong), ("step_launches", C.c_longlong), ("groups", C.c_longlong),
+                ("max_group", C.c_longlong), ("set_launches", C.c_longlong * 2)]
+
+
 def _lib():
     L = host.load_host()
     if not hasattr(L, "_tsqp_ready"):
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        L.thost_tsqp_solve_batch.argtypes = [C.POINTER(Spec), C.POINTER(KinSpec), C.c_int, C.c_int, dp,
+                                             C.POINTER(Result), ip, C.POINTER(BatchStats), C.c_char_p, C.c_int]
+        L.thost_tsqp_solve_batch.restype = C.c_int
+        L.thost_tsqp_sizeof_batch_stats.restype = C.c_int
+        if L.thost_tsqp_sizeof_batch_stats() != C.sizeof(BatchStats):
+            raise RuntimeError("tsqp_batch_stats layout mismatch between Python and the host library")
         L.thost_tsqp_solve_kin.argtypes = [C.POINTER(Spec), C.POINTER(KinSpec), C.c_int, dp, C.POINTER(Result),
                                            C.c_char_p, C.c_int]
         L.thost_tsqp_solve_kin.restype = C.c_int
@@ -171,6 +187,32 @@ def solve(spec: Spec, device: int = 0):
     if rc != 0:
         raise host.HostError(err.value.decode())
     return x, res
+
+
+def solve_batch(specs, kins=None, device: int = 0):
+    """-> (list of x [n_nodes, n_dof], list of Result, qp_rounds [batch], BatchStats): the problems of `specs` (with
+    the kinematic sets of `kins`, one per spec, when given) in lock step on HIP device `device`
+    (thost_tsqp_solve_batch).  Problem b's x and Result are those of solve(specs[b]) / solve_kin(specs[b], kins[b])
+    alone, bit for bit; qp_rounds[b] counts the rounds it took part in.  Raises HostError naming every problem that
+    failed."""
+    L = _lib()
+    B = len(specs)
+    if kins is not None and len(kins) != B:
+        raise ValueError("solve_batch: one KinSpec per Spec")
+    sa = (Spec * max(B, 1))(*specs)
+    ka = None if kins is None else (KinSpec * max(B, 1))(*kins)
+    stride = MAX_NODES * D_MAX
+    x = np.zeros((max(B, 1), stride))
+    res = (Result * max(B, 1))()
+    rounds = np.zeros(max(B, 1), dtype=np.int32)
+    stats = BatchStats()
+    err = C.create_string_buffer(16384)
+    rc = L.thost_tsqp_solve_batch(sa, ka, B, device, x.ctypes.data_as(C.POINTER(C.c_double)), res,
+                                  rounds.ctypes.data_as(C.POINTER(C.c_int)), C.byref(stats), err, 16384)
+    if rc != 0:
+        raise host.HostError(err.value.decode())
+    xs = [x[b, :specs[b].n_nodes * specs[b].n_dof].reshape(specs[b].n_nodes, specs[b].n_dof).copy() for b in range(B)]
+    return xs, [res[b] for b in range(B)], rounds[:B].copy(), stats
 
 
 def make_kin_spec(manip, cart=(), coll=(), prims=None, ccoll=()):
